@@ -22,7 +22,12 @@ inputs resident in HBM when the timed region starts; random numbers are drawn on
 reference draws them per step too).  Multi-GPU: frames shard across ranks with replicated parameters (weak scaling: one
 frame per rank per step), gradients all-reduced over RCCL.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run sets up, warms up, times the K steps and prints the line.  `--dump-outputs DIR` also writes what the last timed
+step computed (DIR/<name>.npy, see dump_outputs).  `--full` adds the measurements beside the headline figure, each in runs of
+its own after the timed steps: the CPU baseline with its parity check, the instrumented per-kernel breakdown and the objects
+priced from it, the deformer-search comparison, config2 and config4 (the `--no-*` options still drop single ones of them).
+
+Extra objects in the line (`--full`; null in a plain run):
   roofline     -- the dominant C-ABI entry point of the step (by HIP-event time measured live on the launch stream).  For the
                   Broyden search ("cache-gather latency") it is priced against the bound that binds it: bytes
                   through the vector-memory (TCP/L1) path from the COUNTED trilinear fetches against 256 CUs x 64 B/clk;
@@ -140,6 +145,51 @@ def cgroup_throttle():
         return None
 
 
+# --dump-outputs: the per-ray maps that RenderStep.forward_backward_phys / forward_backward / forward return to their caller
+DUMP_RAY_MAPS = ("comp_rgb", "comp_rgb_phys", "opacity", "comp_normal", "albedo", "roughness", "metallic")
+DUMP_MAX_RAYS = 1 << 19          # a larger frame is written as a fixed sample of its rays
+DUMP_MAX_ENTRIES = 1 << 17       # per parameter / gradient: a larger tensor is written as a fixed sample of its entries
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, outs, params):
+    """what the timed path computed in its last step, as <path>/<name>.npy (float32; float64 where the tensor is float64):
+    the per-ray maps of DUMP_RAY_MAPS over all ray chunks in ray order, `loss` (one entry per chunk), and per entry i of the step's
+    parameter list `param_<i>` (after the step's optimiser update) and `grad_<i>` (the accumulated gradient that update read).  A frame of more
+    than DUMP_MAX_RAYS rays keeps a fixed sample of its rays (`ray_index`), a tensor of more than DUMP_MAX_ENTRIES entries a fixed
+    sample of its flattened entries; the samples come from fixed seeds, so runs with the same arguments write the same entries."""
+    def host(t):
+        a = t.detach().cpu().numpy()
+        return a if a.dtype == np.float64 else a.astype(np.float32)
+    arrays = {}
+    maps = {k: torch.cat([o[k].reshape(o[k].shape[0], -1) for o in outs]) for k in DUMP_RAY_MAPS
+            if outs and all(torch.is_tensor(o.get(k)) for o in outs)}
+    n_rays = next(iter(maps.values())).shape[0] if maps else 0
+    if n_rays > DUMP_MAX_RAYS:
+        idx = np.sort(np.random.default_rng(0).choice(n_rays, DUMP_MAX_RAYS, replace=False))
+        arrays["ray_index"] = idx.astype(np.float64)
+        sel = torch.from_numpy(idx).to(next(iter(maps.values())).device)
+        maps = {k: v[sel] for k, v in maps.items()}
+    arrays.update({k: host(v) for k, v in maps.items()})
+    if outs and all(torch.is_tensor(o.get("loss")) for o in outs):
+        arrays["loss"] = host(torch.stack([o["loss"].reshape(()) for o in outs]))
+    for i, p in enumerate(params):
+        flat = p.detach().reshape(-1)
+        grad = None if p.grad is None else p.grad.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ENTRIES:
+            idx = np.sort(np.random.default_rng([i, flat.numel()]).choice(flat.numel(), DUMP_MAX_ENTRIES, replace=False))
+            sel = torch.from_numpy(idx).to(flat.device)
+            flat, grad = flat[sel], (None if grad is None else grad[sel])
+        arrays[f"param_{i:03d}"] = host(flat)
+        if grad is not None:
+            arrays[f"grad_{i:03d}"] = host(grad)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes > {DUMP_MAX_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), a)
+
+
 def build_headline(dev, hw, spp, rank, pose):
     """the synthetic frame + material head + training-time light of the headline workload."""
     from intrinsicavatar_amd import synthetic as S, fields, pbr
@@ -194,7 +244,7 @@ def build_config4_step(rs, rays, mat, sg, dev, bg, n_batch=4096, spp=512, seed=4
     return s4, f"{n_batch} rays on the subject of the bench frame, PBR training step (uniform_light, spp {spp}), fwd+bwd+Adam"
 
 
-def measure_config4(rs, rays, mat, sg, dev, bg, n_batch=4096, spp=512, steps=20, rank=0, world=1, rccl_at_one_rank=False):
+def measure_config4(rs, rays, mat, sg, dev, bg, n_batch=4096, spp=512, steps=20, rank=0, world=1, rccl_at_one_rank=False, dump=None):
     """The line's `config4` object -- the reference's 4096-ray training batch per GPU: ms per step, rays/s (whole job: world x n_batch rays per
     step, ray-batch sharding of ONE frame with replicated parameters, BASELINE configs[3]), the search launches of one step (points, ms) --
     the step's one large search batch is its secondary march (~2 100 march points per ray), not the 4096 rays' own samples -- and the
@@ -240,6 +290,8 @@ def measure_config4(rs, rays, mat, sg, dev, bg, n_batch=4096, spp=512, steps=20,
     for _ in range(10):                 # (the first ~30 steps of a process drift down by ~5 %: allocator pools and clocks settle)
         o = s4()
     ms, o = timed(s4, steps)
+    if dump is not None and rank == 0:
+        dump([o], s4.params)                                        # before any later step moves the parameters
     comm = sparse = None
     if sync is not None:
         for _ in range(2):
@@ -322,6 +374,11 @@ def main():
     ap.add_argument("--pose", default=os.environ.get("IA_BENCH_POSE", "male-3-casual:0"),
                     help="frame of the reference's pose files through plain FK: male-3-casual:{0,40,80,113} (peoplesnapshot training frames), "
                          "aist:{0,100,200,319} (animation, out of distribution), or synthetic:K (N(0, 0.25) joint angles, rounds 1-2)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: cpu_baseline + parity_on_bench_frame, the instrumented "
+                         "breakdown (roofline, mfma, hash_gather), deformer_search, config2 and config4 (off: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-config2", action="store_true", help="skip the secondary configs[1] measurement of the headline line")
     ap.add_argument("--no-config4", action="store_true", help="skip the 4096-ray training-batch measurement (configs[3] shape) of the headline line")
@@ -333,6 +390,8 @@ def main():
     ap.add_argument("--pass", dest="mode", choices=["fwd+bwd", "fwd"], default="fwd+bwd",
                     help="fwd+bwd = training-step form of render_step (BASELINE metric); fwd = inference form (config2 only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     self_launch_ranks(args.gpus)                 # plain `python bench.py --gpus N`: start the N ranks ourselves
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -404,7 +463,8 @@ def main():
     if args.workload == "config4":
         # BASELINE configs[3] on its own: K timed steps of the 4096-ray training batch per rank (ray-batch sharding of one frame)
         c4 = measure_config4(rs, rays, mat, sg, dev, torch.ones(3, device=dev), steps=max(args.steps, 1), rank=rank, world=world,
-                             rccl_at_one_rank=force_rccl)
+                             rccl_at_one_rank=force_rccl,
+                             dump=(lambda outs, ps: dump_outputs(args.dump_outputs, outs, ps)) if args.dump_outputs else None)
         if rank == 0:
             line = {"metric": "rays/sec (fwd+bwd), 4096-ray training batches per GPU (BASELINE configs[3]: uniform_light, spp 512)",
                     "value": c4 and c4["rays_per_s"], "unit": "rays/s", "n_gpus": world, "steps": max(args.steps, 1), "warmup": 10,
@@ -450,8 +510,9 @@ def main():
 
     totals = {}
 
-    def step_headline(sync=None):
-        """one 540x540 frame: fwd + bwd with the PBR branch at `spp`, chunked with gradient accumulation."""
+    def step_headline(sync=None, keep=False):
+        """one 540x540 frame: fwd + bwd with the PBR branch at `spp`, chunked with gradient accumulation.
+        keep: the result also holds what every chunk's forward_backward_phys returned (`chunks`, for --dump-outputs)."""
         zero_grads()
         # training-time light: SG lobes -> equirect image (differentiable); the chunks share one image and its gradient
         # is accumulated in a leaf and pushed through generate_image() once at the end
@@ -470,6 +531,7 @@ def main():
                 img.backward(leaf.grad)
             totals.update(tot)
             return dict(stats=tot)
+        kept = []
         for ci, (r, t, m, frac) in enumerate(chunk_views):
             last = ci == len(chunk_views) - 1
             ctx = sync.no_sync() if (sync is not None and not last) else _null()
@@ -479,11 +541,13 @@ def main():
                                              light_sampling="per_point", loss_scale=frac)
             for k in tot:
                 tot[k] += int(o["stats"].get(k, 0))
+            if keep:
+                kept.append({k: o[k].detach() for k in DUMP_RAY_MAPS + ("loss",) if k in o})
             del o
         if leaf.grad is not None:
             img.backward(leaf.grad)
         totals.update(tot)
-        return dict(stats=tot)
+        return dict(stats=tot, chunks=kept) if keep else dict(stats=tot)
 
     import contextlib
     _null = contextlib.nullcontext
@@ -517,8 +581,8 @@ def main():
         opt, sched = optim.reference_optimizer(rs, grad_scale=1.0 / world, material=mat if headline else None,
                                                emitter=sg if headline else None)
 
-    def step():
-        out = step_headline(sync) if headline else step_config2(sync)
+    def step(keep=False):
+        out = step_headline(sync, keep) if headline else step_config2(sync)
         if sync is not None:
             reduced_bytes[0] = sync.finish()
         if opt is not None:
@@ -529,7 +593,7 @@ def main():
     # CPU baseline + parity at the bench frame, BEFORE the first optimiser step: the oracle's scene bundle holds the parameters as
     # initialised, and the same rays go through the GPU path with the same random numbers right after the workers finish
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from intrinsicavatar_amd import synthetic as _S
         env0 = sg.generate_image().detach() if headline else None
         cpu, parity = cpu_baseline(rays, export, n_rays, headline, args.spp, _S.export_phys(mat, env0) if headline else None,
@@ -547,8 +611,8 @@ def main():
     thr0 = cgroup_throttle()
     cpu0 = time.process_time()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        out = step()
+    for i in range(args.steps):
+        out = step(keep=bool(args.dump_outputs) and i == args.steps - 1)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -557,6 +621,10 @@ def main():
     peak_alloc_timed, peak_reserved_timed = torch.cuda.max_memory_allocated(), torch.cuda.max_memory_reserved()
     cpu_busy = (time.process_time() - cpu0) / max(dt, 1e-9)          # CPUs this rank kept busy during the timed region
     thr1 = cgroup_throttle()
+    if args.dump_outputs and rank == 0:
+        # what the last timed step computed, before any later step moves the parameters
+        dump_outputs(args.dump_outputs, out.get("chunks", [out]), params)
+        out.pop("chunks", None)
     # ---- ONE more step with a HIP-event pair around every C-ABI launch (on the launch stream): per-kernel durations
     # and counted units for the roofline / breakdown.  Kept out of the throughput region because the event records cost
     # host time that the un-instrumented step does not pay (ms_per_step_instrumented is reported next to it).
@@ -570,13 +638,14 @@ def main():
     detail, dt_instr, k_instr = {}, 0.0, 0
     # The instrumented step runs the secondary march on ONE stream: a roofline prices a kernel that has the device to itself, and the
     # timed region's streams (render.RenderStep.SECONDARY_STREAMS) let launches of two chunks share it.
+    breakdown_on = args.full and not args.no_breakdown
     timed_streams = rs.SECONDARY_STREAMS
     rs.SECONDARY_STREAMS = 1
-    if timed_streams > 1 and not args.no_breakdown:
+    if timed_streams > 1 and breakdown_on:
         torch.cuda.empty_cache()          # the working set moves from the side streams' pools to the caller's: hand the cached blocks back first
         step()                            # ... and one untimed step to fill the caller's pool again (~130 GiB of hipMalloc)
         torch.cuda.synchronize()
-    if not args.no_breakdown:
+    if breakdown_on:
         k_instr = 1 if headline else args.steps
         lib.start()
         t1 = time.perf_counter()
@@ -589,7 +658,7 @@ def main():
             for name_, calls_ in sorted(detail.items(), key=lambda kv: -sum(c[0] for c in kv[1]))[:10]:
                 print(name_, [(round(c[0], 2), c[1]) for c in calls_], file=sys.stderr)
     rs.SECONDARY_STREAMS = timed_streams
-    if timed_streams > 1 and not args.no_breakdown:
+    if timed_streams > 1 and breakdown_on:
         torch.cuda.empty_cache()
     if world > 1:
         t = torch.tensor([dt], device=dev)
@@ -602,7 +671,7 @@ def main():
     # filter.cu:10-54), IN THIS RUN: (i) the same step with the early filter off (spec_eps = 0: every search runs to its end, K9 as a
     # pass) timed next to the timed figure; (ii) on march points of this frame, the candidate sets / min-SDF of the two searches compared
     search_modes = None
-    if headline and rank == 0 and world == 1 and not args.no_search_modes and rs.deformer.spec_eps > 0:
+    if headline and rank == 0 and world == 1 and args.full and not args.no_search_modes and rs.deformer.spec_eps > 0:
         eps0 = rs.deformer.spec_eps
         try:
             rs.deformer.spec_eps = 0.0
@@ -662,7 +731,7 @@ def main():
 
     # ---- secondary key of the headline line: round 1's configs[1] step (radiance + SDF, no PBR branch), same frame
     config2 = None
-    if headline and rank == 0 and world == 1 and not args.no_config2:
+    if headline and rank == 0 and world == 1 and args.full and not args.no_config2:
         opt2, sched2 = optim.reference_optimizer(rs)
 
         def s2():
@@ -684,7 +753,7 @@ def main():
     # ---- third key: BASELINE configs[3] shape = the reference's OWN training batch (configs/sampler/edge.yaml:2: 4096 rays per step
     # and GPU; PBR branch, render_mode=uniform_light, spp 512, fwd + bwd + Adam), rays drawn on the subject of the same frame
     config4 = None
-    if headline and not args.no_config4:
+    if headline and args.full and not args.no_config4:
         # EVERY rank: at N > 1 the batches are sharded over the ranks and the gradients meet in the all-reduce (the regime where the
         # 101 MB exchange is a visible share of a step, unlike the 300 ms headline step)
         if sync is not None:

@@ -121,9 +121,9 @@ def test_bench_starts_its_own_ranks():
 
 
 def test_bench_line_of_one_rank_carries_the_objects_the_contract_names():
-    """`python bench.py` on one GPU (small frame): ONE JSON line with the contract's keys, `roofline` and `cpu_baseline`, and the
+    """`python bench.py --full` on one GPU (small frame): ONE JSON line with the contract's keys, `roofline` and `cpu_baseline`, and the
     secondary workloads `config4` (the reference's 4096-ray training batch) and `config2_ms_per_step`."""
-    line = _run_line(["bench.py", "--steps", "1", "--warmup", "1", "--hw", "96", "--spp", "16", "--no-search-modes"])
+    line = _run_line(["bench.py", "--full", "--steps", "1", "--warmup", "1", "--hw", "96", "--spp", "16", "--no-search-modes"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):
         assert k in line, k
@@ -133,6 +133,25 @@ def test_bench_line_of_one_rank_carries_the_objects_the_contract_names():
     c4 = line["config4"]
     assert c4 is not None and c4["ms_per_step"] > 0 and c4["secondary_rays_per_step"] > 0 and len(c4["search_launches_ms_points"]) >= 3
     assert line["config2_ms_per_step"] > 0
+
+
+def test_plain_bench_line_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """the plain command form without --full: the K timed steps and nothing beside them (every object of --full is null), and
+    --dump-outputs writes what the last timed step computed (per-ray maps, loss, parameters and gradients) as .npy files."""
+    import numpy as np
+    d = tmp_path / "outputs"
+    line = _run_line(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--hw", "64", "--spp", "16", "--dump-outputs", str(d)])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["dtype"] == "f32"
+    for k in ("roofline", "mfma", "hash_gather", "cpu_baseline", "parity_on_bench_frame", "deformer_search", "config4", "config2_ms_per_step"):
+        assert line[k] is None, k
+    got = {f.stem: np.load(f) for f in d.glob("*.npy")}
+    for k in ("comp_rgb", "comp_rgb_phys", "opacity", "albedo"):
+        assert got[k].shape[0] == 64 * 64 and got[k].dtype == np.float32 and np.isfinite(got[k]).all(), k
+    assert got["loss"].shape == (1,) and np.isfinite(got["loss"]).all()
+    params = [k for k in got if k.startswith("param_")]
+    assert len(params) >= 4 and any(k.startswith("grad_") for k in got)
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
 
 
 def test_relight_bench_starts_its_own_ranks():
@@ -209,7 +228,7 @@ def test_bench_step_through_rccl_on_one_rank():
     env = dict(os.environ, IA_BENCH_FORCE_RCCL="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--hw", "64", "--spp", "16", "--ray-chunk", "2048",
+    p = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--hw", "64", "--spp", "16", "--ray-chunk", "2048",
                         "--no-cpu-baseline", "--no-config2", "--no-config4", "--no-search-modes"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
