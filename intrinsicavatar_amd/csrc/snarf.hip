@@ -94,7 +94,30 @@ __device__ __forceinline__ void load_corner(const float* __restrict__ vJ, int64_
     }
 }
 
-template <int LAYOUT, bool PAIRS = false>
+// the 12 channels of one corner through the SCALAR memory path: `off` is wave-uniform (a readfirstlane value), the loads go through the
+// constant address space and become s_load_dwordx8 + s_load_dwordx4 into SGPRs -- no vector-L1 (TCP) request for any lane.  The
+// channels travel as six 64-bit pairs (one v_mov_b64 each where the lanes take them over from the SGPRs)
+typedef uint64_t ia_u64x4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint64_t ia_u64x2 __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint64_t ia_u64x2v __attribute__((ext_vector_type(2), aligned(16)));
+__device__ __forceinline__ void load_corner_scalar(const char* base, uint32_t off, uint64_t q[6])
+{
+    const __attribute__((address_space(4))) char* cb = (const __attribute__((address_space(4))) char*)base;
+    const ia_u64x4 lo = *(const __attribute__((address_space(4))) ia_u64x4*)(cb + off);
+    const ia_u64x2 hi = *(const __attribute__((address_space(4))) ia_u64x2*)(cb + off + 32u);
+    q[0] = lo[0]; q[1] = lo[1]; q[2] = lo[2]; q[3] = lo[3]; q[4] = hi[0]; q[5] = hi[1];
+}
+__device__ __forceinline__ void load_corner_vector(const char* base, uint32_t off, uint64_t q[6])
+{
+    const ia_u64x2v p0 = *reinterpret_cast<const ia_u64x2v*>(base + off);
+    const ia_u64x2v p1 = *reinterpret_cast<const ia_u64x2v*>(base + off + 16u);
+    const ia_u64x2v p2 = *reinterpret_cast<const ia_u64x2v*>(base + off + 32u);
+    q[0] = p0[0]; q[1] = p0[1]; q[2] = p1[0]; q[3] = p1[1]; q[4] = p2[0]; q[5] = p2[1];
+}
+
+// SCELLS (channel-last x-pair fetch only): 1 = the lanes in the voxel cell of the wave's first active lane (the LEADER) take their
+// corners through the scalar path, 0 = every lane loads its own
+template <int LAYOUT, bool PAIRS = false, int SCELLS = 0>
 __device__ __forceinline__ void grid_sample_J(const float* __restrict__ vJ, int vox0, int D, int H, int W, float gx, float gy,
                                               float gz, float out[12])
 {
@@ -143,6 +166,17 @@ __device__ __forceinline__ void grid_sample_J(const float* __restrict__ vJ, int 
         // +0 and can only become -0 from two -0 addends), so the result is the reference's, which skips such corners.
         const char* base = reinterpret_cast<const char*>(vJ);
         // (a wave-uniform fast path without the selects, for waves whose lanes all have both x-corners in range, measured no gain)
+        // SCELLS: the vector-L1 request path is the search kernel's bound, and it costs per active lane -- also when every lane of the
+        // wave reads the same voxel.  A third of the lane-fetches fall in the cell of the wave's first active lane: those lanes (the
+        // leader GROUP: all three cell coordinates equal -- the range flags, and so the corners read, are then the leader's; lin0 alone
+        // aliases across rows at x0 = -1 / W) take the phase's two corners from ONE wave-uniform scalar load instead of six vector
+        // loads each.  Same bytes, same packed mul / add with the lane's own weights: bit-identical.  Serving the cell of the first lane
+        // outside the leader group the same way as well (+21 % of the lane-fetches) measured slower: search 9.32 against 8.09 ms.
+        bool lead = false;
+        if (SCELLS == 1) {
+            const int lx = __builtin_amdgcn_readfirstlane(x0), ly = __builtin_amdgcn_readfirstlane(y0), lz = __builtin_amdgcn_readfirstlane(z0);
+            lead = x0 == lx && y0 == ly && z0 == lz;
+        }
 #pragma unroll
         for (int e = 0; e < 4; e++) {
             const bool okyz = oky[e & 1] && okz[(e >> 1) & 1];
@@ -151,19 +185,36 @@ __device__ __forceinline__ void grid_sample_J(const float* __restrict__ vJ, int 
                 const uint32_t b0 = boff0 + cst + (okx[0] ? 0u : 48u);                                // corner x0 (or x1's voxel if x0 is outside)
                 const uint32_t b1 = boff0 + cst + (okx[1] ? 48u : 0u);                                // corner x1 (or x0's voxel)
                 const float w0 = okx[0] ? wgt[2 * e] : 0.0f, w1 = okx[1] ? wgt[2 * e + 1] : 0.0f;
-                const float4 a0 = *reinterpret_cast<const float4*>(base + b0);
-                const float4 a1 = *reinterpret_cast<const float4*>(base + b0 + 16u);
-                const float4 a2 = *reinterpret_cast<const float4*>(base + b0 + 32u);
-                const float4 c0 = *reinterpret_cast<const float4*>(base + b1);
-                const float4 c1 = *reinterpret_cast<const float4*>(base + b1 + 16u);
-                const float4 c2 = *reinterpret_cast<const float4*>(base + b1 + 32u);
-                const v2f u0 = (v2f){w0, w0}, u1 = (v2f){w1, w1};
-                acc2[0] = acc2[0] + (v2f){a0.x, a0.y} * u0; acc2[1] = acc2[1] + (v2f){a0.z, a0.w} * u0;
-                acc2[2] = acc2[2] + (v2f){a1.x, a1.y} * u0; acc2[3] = acc2[3] + (v2f){a1.z, a1.w} * u0;
-                acc2[4] = acc2[4] + (v2f){a2.x, a2.y} * u0; acc2[5] = acc2[5] + (v2f){a2.z, a2.w} * u0;
-                acc2[0] = acc2[0] + (v2f){c0.x, c0.y} * u1; acc2[1] = acc2[1] + (v2f){c0.z, c0.w} * u1;
-                acc2[2] = acc2[2] + (v2f){c1.x, c1.y} * u1; acc2[3] = acc2[3] + (v2f){c1.z, c1.w} * u1;
-                acc2[4] = acc2[4] + (v2f){c2.x, c2.y} * u1; acc2[5] = acc2[5] + (v2f){c2.z, c2.w} * u1;
+                if constexpr (SCELLS == 0) {       // (kept as written: the exact small-batch kernel and IA_BR_SPEC_SCALAR=0 compile as before)
+                    const float4 a0 = *reinterpret_cast<const float4*>(base + b0);
+                    const float4 a1 = *reinterpret_cast<const float4*>(base + b0 + 16u);
+                    const float4 a2 = *reinterpret_cast<const float4*>(base + b0 + 32u);
+                    const float4 c0 = *reinterpret_cast<const float4*>(base + b1);
+                    const float4 c1 = *reinterpret_cast<const float4*>(base + b1 + 16u);
+                    const float4 c2 = *reinterpret_cast<const float4*>(base + b1 + 32u);
+                    const v2f u0 = (v2f){w0, w0}, u1 = (v2f){w1, w1};
+                    acc2[0] = acc2[0] + (v2f){a0.x, a0.y} * u0; acc2[1] = acc2[1] + (v2f){a0.z, a0.w} * u0;
+                    acc2[2] = acc2[2] + (v2f){a1.x, a1.y} * u0; acc2[3] = acc2[3] + (v2f){a1.z, a1.w} * u0;
+                    acc2[4] = acc2[4] + (v2f){a2.x, a2.y} * u0; acc2[5] = acc2[5] + (v2f){a2.z, a2.w} * u0;
+                    acc2[0] = acc2[0] + (v2f){c0.x, c0.y} * u1; acc2[1] = acc2[1] + (v2f){c0.z, c0.w} * u1;
+                    acc2[2] = acc2[2] + (v2f){c1.x, c1.y} * u1; acc2[3] = acc2[3] + (v2f){c1.z, c1.w} * u1;
+                    acc2[4] = acc2[4] + (v2f){c2.x, c2.y} * u1; acc2[5] = acc2[5] + (v2f){c2.z, c2.w} * u1;
+                } else {
+                    uint64_t qa[6], qc[6];                                                            // channel pairs of the two corners
+                    // (inside the branch the first active lane is the leader, and every lane there has the leader's b0 / b1)
+                    if (lead) {
+                        load_corner_scalar(base, __builtin_amdgcn_readfirstlane(b0), qa);
+                        load_corner_scalar(base, __builtin_amdgcn_readfirstlane(b1), qc);
+                    } else {
+                        load_corner_vector(base, b0, qa);
+                        load_corner_vector(base, b1, qc);
+                    }
+                    const v2f u0 = (v2f){w0, w0}, u1 = (v2f){w1, w1};
+#pragma unroll
+                    for (int k = 0; k < 6; k++) acc2[k] = acc2[k] + __builtin_bit_cast(v2f, qa[k]) * u0;
+#pragma unroll
+                    for (int k = 0; k < 6; k++) acc2[k] = acc2[k] + __builtin_bit_cast(v2f, qc[k]) * u1;
+                }
             }
         }
     } else {
@@ -650,7 +701,7 @@ struct SpecFlag {
 // x [N, SPEC_ROOTS, 3] slot k, and the lane leaves cnt[point] and meta[point] = the inits of slots 0..2 in bytes 0..2: 44 bytes per
 // point instead of 169 (x [N,I,3] + is_valid [N,I]), no filter pass.  Flagged points leave cnt = 0 and their record; rows_flagged_kernel
 // fills in their rows (and overflow records for a 4th, 5th ... survivor).
-template <bool COUNT, bool PACK, int WG = THREADS>
+template <bool COUNT, bool PACK, int WG = THREADS, int SCELLS = 0>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(IA_BR2_WAVES, IA_BR2_WAVES))) void broyden_spec_kernel(
     int64_t N, int I, const float* __restrict__ xd_tgt, const float* __restrict__ voxel_J, int D, int H, int W,
     const float* __restrict__ tfs, const int32_t* __restrict__ bone_ids, const float* __restrict__ offset_g,
@@ -810,7 +861,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(IA_BR2_WAVES
         const float iy = scale[1] * (x_l[1] + offset[1]);
         const float iz = scale[2] * (x_l[2] + offset[2]);
         float Jl[12];
-        grid_sample_J<IA_LAYOUT_NDHWC, true>(voxel_J, 0, D, H, W, ix, iy, iz, Jl);
+        grid_sample_J<IA_LAYOUT_NDHWC, true, SCELLS>(voxel_J, 0, D, H, W, ix, iy, iz, Jl);
 #ifdef IA_SPEC_DIAG_ITERS       /* diagnostic build: counters[4] = lane-slots of the fetch iterations (64 per wave iteration that fetched) */
         if (COUNT) { c_fetch++; c_corner += (__ffsll((long long)__ballot(1)) - 1 == lane) ? 64u : 0u; }      // exact: one lane of the wave adds the 64 slots
 #ifdef IA_SPEC_DIAG_CELLS       /* counters[1] = fetches in the voxel cell of the wave's first active lane, counters[2] = ... of the first lane outside that cell */
@@ -1651,10 +1702,19 @@ static int launch_spec(bool pack, int64_t N, int I, const float* xd_tgt, const f
     // needs no LDS -- the hash gather, 104 VGPRs).  Used with the search token of deformer.py (one search on the device at a time).
     static int pad_lds = -1;
     if (pad_lds < 0) { const char* e = getenv("IA_BR_SPEC_PAD_LDS"); const int v = e ? atoi(e) : 0; pad_lds = (v > 0 && v <= 32768) ? v : 0; }
+    // IA_BR_SPEC_SCALAR = 1 (default): the leader cell of each wave's fetch is served through the scalar memory path (grid_sample_J's
+    // SCELLS); 0: every lane through the vector path.  Read at every launch: a same-process A/B and the tests switch it without a rebuild.
+    int scells = 1;
+    if (const char* e = getenv("IA_BR_SPEC_SCALAR")) scells = atoi(e) == 0 ? 0 : 1;
+#define IA_SPEC_LAUNCH_S(COUNT, PACK, SC)                                                                                                    \
+    broyden_spec_kernel<COUNT, PACK, THREADS, SC><<<grid, THREADS, pad_lds, s>>>(N, I, xd_tgt, voxel_J_cl, D, H, W, tfs, bone_ids, offset, scale, \
+                                                                                 cvg_threshold, dvg_threshold, eps, x, J_inv, is_valid, fwd_J, pts, c, \
+                                                                                 cnt, meta, flag, slots, order, cell_tight)
 #define IA_SPEC_LAUNCH(COUNT, PACK)                                                                                                    \
-    broyden_spec_kernel<COUNT, PACK><<<grid, THREADS, pad_lds, s>>>(N, I, xd_tgt, voxel_J_cl, D, H, W, tfs, bone_ids, offset, scale,   \
-                                                               cvg_threshold, dvg_threshold, eps, x, J_inv, is_valid, fwd_J, pts, c, cnt, \
-                                                               meta, flag, slots, order, cell_tight)
+    do {                                                                                                                               \
+        if (scells == 0) IA_SPEC_LAUNCH_S(COUNT, PACK, 0);                                                                             \
+        else IA_SPEC_LAUNCH_S(COUNT, PACK, 1);                                                                                         \
+    } while (0)
     if (pack && !counters && wg_env != THREADS) {
         // A / B: smaller workgroups (one point per lane each): IA_BR_SPEC_WG = 64 | 128, chunk = the workgroup's lanes
         if (wg_env == 64)
@@ -1669,6 +1729,7 @@ static int launch_spec(bool pack, int64_t N, int I, const float* xd_tgt, const f
     if (pack) { if (counters) IA_SPEC_LAUNCH(true, true); else IA_SPEC_LAUNCH(false, true); }
     else { if (counters) IA_SPEC_LAUNCH(true, false); else IA_SPEC_LAUNCH(false, false); }
 #undef IA_SPEC_LAUNCH
+#undef IA_SPEC_LAUNCH_S
     return ia::check_launch(what);
 }
 
