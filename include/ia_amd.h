@@ -740,6 +740,24 @@ int ia_edge_min_sdf(int64_t n_edges, const float* sdf, const uint8_t* is_left, f
  * k = 0,1,2; 1: separate products left to right; 2: fma chain k = 2,1,0). */
 int ia_transform_rays_w2s(int64_t n, const float* rays, int ray_stride, const float* w2s, int variant, float* out, ia_stream_t stream);
 
+/* ------------------------------------------------------------------------- */
+/* Canonical mesh export (csrc/mcubes.hip): MarchingCubeHelper.forward / BaseImplicitGeometry.isosurface_ (models/rf/geometry.py:14-104)
+ * on the device.  Conventions (inside test, vertex placement, vertex / face order, winding): csrc/mc_math.h and DESIGN.md.
+ *
+ * ia_mc_count: level [nx,ny,nz] fp32 C order (nx, ny, nz >= 2, fewer than 2^31 points) -> totals [2] int64 on the device = (vertices,
+ *   triangles); scratch: ia_mc_scratch_bytes(nx, ny, nz) bytes, handed on unchanged to ia_mc_emit.
+ * ia_mc_emit: box (HOST [6]: vmin xyz, vmax xyz) -> v_pos [V,3] fp32 = scale_anything(index coordinate / (n - 1), (0,1), (vmin, vmax)),
+ *   t_pos_idx [T,3] int64; first_vid [nx*ny*nz] int32 work table (V must fit int32).  Launch only when V > 0.
+ * ia_mc_grid_points: normalized hash-grid coordinates [n,3] of grid points [start, start + n) (C order over [nx,ny,nz]):
+ *   (axis value - center) / scale + 0.5 with axes = [nx + ny + nz] per-axis coordinates (isosurface_'s scale_anything of linspace(0, 1)),
+ *   center, scale [3] on the device -- the arithmetic of ia_normalize_points on the grid isosurface_ builds. */
+int64_t ia_mc_scratch_bytes(int nx, int ny, int nz);
+int ia_mc_count(int nx, int ny, int nz, const float* level, float threshold, void* scratch, int64_t* totals, ia_stream_t stream);
+int ia_mc_emit(int nx, int ny, int nz, const float* level, float threshold, const float* box, const void* scratch, int32_t* first_vid,
+               float* v_pos, int64_t* t_pos_idx, ia_stream_t stream);
+int ia_mc_grid_points(int64_t n, int64_t start, int nx, int ny, int nz, const float* axes, const float* center, const float* scale,
+                      float* out, ia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ SOURCES = {
     "occgrid.hip": [],
     "optim.hip": ["-ffp-contract=off"],
     "stepops.hip": ["-ffp-contract=off"],
+    "mcubes.hip": ["-ffp-contract=off"],
 }
 
 

@@ -313,7 +313,15 @@ class VolumeSDF(nn.Module):
     def prepare_bbox(self, bbox: Tensor):
         self.center = ((bbox[0] + bbox[1]) / 2).to(self.center)
         self.scale = (bbox[1] - bbox[0]).to(self.scale)
+        self.bbox = bbox                   # the canonical bbox isosurface() extracts the mesh in (rf/geometry.py:61-68)
         self._inv_scale_host = None
+
+    def isosurface(self):
+        """BaseImplicitGeometry.isosurface (rf/geometry.py:94-104) with the settings of self.isosurface_config (mesh.ISOSURFACE:
+        configs/geometry/progressive_hash_grid.yaml) -> {"v_pos", "t_pos_idx"} on the device."""
+        from . import mesh
+        cfg = getattr(self, "isosurface_config", None) or mesh.ISOSURFACE
+        return mesh.isosurface(self, cfg["resolution"], cfg["chunk"], cfg["threshold"])
 
     def inv_scale_host(self):
         """1 / scale as python floats for the kernels' host-side arguments; read back once per bbox, not once per step."""

@@ -6,6 +6,7 @@
     rgb_image_u8 / grayscale_image_u8 / image_grid_u8 / save_image_grid
                                  the panels the reference's SaverMixin writes per validation / test image
                                  (utils/mixins.py:43-58, 87-122, 124-155), as RGB uint8 arrays / PNG files via PIL
+    save_obj / load_obj          the exported mesh (SaverMixin.save_mesh's `.obj`) as plain `v` / `f` lines, without trimesh
 
 `.exr` needs OpenEXR, which this image does not have: load_hdri raises for it.  Checkpoint key layout and SMPL kinematics are
 covered in checkpoint-facing modules (fields.py, smpl.py)."""
@@ -171,3 +172,36 @@ def save_image_grid(path: str, imgs: Sequence) -> np.ndarray:
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     Image.fromarray(img).save(path)
     return img
+
+
+# ----------------------------------------------------------------------------- Wavefront OBJ (the exported mesh)
+def save_obj(path: str, v_pos, t_pos_idx) -> None:
+    """SaverMixin.save_mesh's `.obj` without trimesh: one `v x y z` line per vertex (%.9g: float32 values round-trip exactly) and one
+    `f a b c` line per face with 1-based indices, in the given order (no vertex merging, no normals, no colour)."""
+    v = np.ascontiguousarray(_np(v_pos), dtype=np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(_np(t_pos_idx), dtype=np.int64).reshape(-1, 3)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as fh:
+        if len(v):
+            np.savetxt(fh, v.astype(np.float64), fmt="v %.9g %.9g %.9g")
+        if len(f):
+            np.savetxt(fh, f + 1, fmt="f %d %d %d")
+
+
+def load_obj(path: str):
+    """(v_pos float32 [V,3], t_pos_idx int64 [T,3] 0-based) of the `v` and triangular `f` lines of an `.obj` (as save_obj writes them;
+    `f a/b/c` index forms keep the position index)."""
+    vs: List[List[float]] = []
+    fs: List[List[int]] = []
+    with open(path) as fh:
+        for line in fh:
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                vs.append([float(t) for t in tok[1:4]])
+            elif tok[0] == "f":
+                if len(tok) != 4:
+                    raise ValueError(f"{path}: only triangular faces are supported")
+                fs.append([int(t.split("/")[0]) - 1 for t in tok[1:4]])
+    return np.array(vs, dtype=np.float32).reshape(-1, 3), np.array(fs, dtype=np.int64).reshape(-1, 3)

@@ -1,0 +1,162 @@
+"""Canonical mesh export: the isosurface of the SDF by marching cubes on the GPU (models/rf/geometry.py:14-104,
+models/intrinsic_avatar.py:277-279 and 1685-1701, systems/intrinsic_avatar.py:923-930).
+
+    marching_cubes(level, threshold, vmin, vmax)   MarchingCubeHelper.forward (+ isosurface_'s vertex scaling) on a device grid
+    isosurface(geometry, resolution, chunk, threshold)
+                                                   BaseImplicitGeometry.isosurface: coarse pass over the geometry's bbox, fine pass
+                                                   over the coarse mesh's extent grown by 10 % (clamped to the bbox)
+    export(geometry, export_config)                IntrinsicAvatar.export: the mesh alone (the reference attaches no vertex colour)
+
+The grid points, the SDF (VolumeSDF.sdf_only, chunk by chunk) and the extraction (csrc/mcubes.hip) stay on the device; a marching-cubes
+call reads back its two output sizes once, isosurface() additionally the coarse mesh's extent (6 floats).  Conventions of the
+extraction: csrc/mc_math.h and DESIGN.md "Mesh export".
+
+    python -m intrinsicavatar_amd.mesh --state-dict CKPT --bbox x0 y0 z0 x1 y1 z1 [--resolution 512] [--global-step 25000] --out mesh.obj
+"""
+import argparse
+import ctypes as C
+import sys
+from typing import Dict, Optional, Sequence
+
+import torch
+
+from . import _lib as L
+
+# configs/geometry/progressive_hash_grid.yaml:6-10
+ISOSURFACE = dict(method="mc", resolution=512, chunk=2097152, threshold=0.0)
+
+
+def _box(vmin, vmax):
+    lo = [0.0, 0.0, 0.0] if vmin is None else [float(v) for v in vmin]
+    hi = [1.0, 1.0, 1.0] if vmax is None else [float(v) for v in vmax]
+    return (C.c_float * 6)(*lo, *hi)
+
+
+@torch.no_grad()
+def marching_cubes(level: torch.Tensor, threshold: float = 0.0, vmin: Optional[Sequence[float]] = None,
+                   vmax: Optional[Sequence[float]] = None) -> Dict[str, torch.Tensor]:
+    """level [nx,ny,nz] fp32 on the GPU -> {"v_pos": [V,3] fp32, "t_pos_idx": [T,3] int64} on the same device.
+    mcubes.marching_cubes(-level, threshold): a grid point is inside iff -level > threshold; vertices are index coordinates / (n - 1),
+    then scale_anything((0,1) -> (vmin, vmax)) per axis when a box is given (float32 values)."""
+    if level.dim() != 3 or min(level.shape) < 2:
+        raise ValueError(f"marching_cubes needs a [nx, ny, nz] grid with every side >= 2, got {tuple(level.shape)}")
+    if level.dtype != torch.float32:
+        raise TypeError("marching_cubes needs a float32 level grid")
+    level = level.contiguous()
+    nx, ny, nz = (int(s) for s in level.shape)
+    lib, st, dev = L.lib(), L.stream(), level.device
+    scratch = torch.empty(int(lib.ia_mc_scratch_bytes(L.i32(nx), L.i32(ny), L.i32(nz))), dtype=torch.uint8, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    thr = L.f32(float(threshold))
+    L.check(lib.ia_mc_count(L.i32(nx), L.i32(ny), L.i32(nz), L.ptr(level), thr, L.ptr(scratch), L.ptr(totals), st), "ia_mc_count")
+    n_v, n_t = (int(v) for v in totals.tolist())             # the one read-back: sizes of the outputs
+    if n_v >= 2 ** 31:
+        raise ValueError(f"marching_cubes: {n_v} vertices do not fit the int32 vertex-id table")
+    v_pos = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
+    t_pos_idx = torch.empty((n_t, 3), dtype=torch.int64, device=dev)
+    if n_v > 0:
+        first_vid = torch.empty(nx * ny * nz, dtype=torch.int32, device=dev)
+        L.check(lib.ia_mc_emit(L.i32(nx), L.i32(ny), L.i32(nz), L.ptr(level), thr, _box(vmin, vmax), L.ptr(scratch), L.ptr(first_vid),
+                               L.ptr(v_pos), L.ptr(t_pos_idx), st), "ia_mc_emit")
+    return {"v_pos": v_pos, "t_pos_idx": t_pos_idx}
+
+
+def grid_axes(resolution: int, vmin: torch.Tensor, vmax: torch.Tensor) -> torch.Tensor:
+    """[3, R] float32 (host): isosurface_'s scale_anything(linspace(0, 1, R), (0, 1), (vmin[a], vmax[a])) per axis -- the coordinates
+    the reference's meshgrid combines, element for element."""
+    lin = torch.linspace(0, 1, resolution)
+    return torch.stack([((lin - 0) / (1 - 0)) * (vmax[a] - vmin[a]) + vmin[a] for a in range(3)])
+
+
+def fine_bbox(vmin: torch.Tensor, vmax: torch.Tensor, bbox: torch.Tensor):
+    """BaseImplicitGeometry.isosurface: the coarse mesh's extent grown by 10 % of itself, clamped to the bbox (float32, host)."""
+    vmin_ = (vmin - (vmax - vmin) * 0.1).clamp(bbox[0], bbox[1])
+    vmax_ = (vmax + (vmax - vmin) * 0.1).clamp(bbox[0], bbox[1])
+    return vmin_, vmax_
+
+
+@torch.no_grad()
+def level_grid(geometry, resolution: int, vmin: torch.Tensor, vmax: torch.Tensor, chunk: int = ISOSURFACE["chunk"]) -> torch.Tensor:
+    """SDF of the R^3 grid over [vmin, vmax] ([R,R,R] fp32 on the geometry's device): grid points straight into the hash grid's
+    normalized coordinates (ia_mc_grid_points), then VolumeSDF.sdf_only chunk by chunk (values do not depend on the chunk)."""
+    R = int(resolution)
+    dev = geometry.center.device
+    axes = grid_axes(R, vmin, vmax).reshape(-1).to(dev)
+    n = R ** 3
+    level = torch.empty(n, dtype=torch.float32, device=dev)
+    chunk = max(1, min(int(chunk), n))
+    xp = torch.empty((chunk, 3), dtype=torch.float32, device=dev)
+    lib = L.lib()
+    center, scale = geometry.center.contiguous().float(), geometry.scale.contiguous().float()
+    for start in range(0, n, chunk):
+        m = min(chunk, n - start)
+        L.check(lib.ia_mc_grid_points(L.i64(m), L.i64(start), L.i32(R), L.i32(R), L.i32(R), L.ptr(axes), L.ptr(center), L.ptr(scale),
+                                      L.ptr(xp), L.stream()), "ia_mc_grid_points")
+        level[start:start + m] = geometry.sdf_only(xp[:m], normalized=True)
+    return level.view(R, R, R)
+
+
+@torch.no_grad()
+def isosurface_(geometry, vmin: torch.Tensor, vmax: torch.Tensor, resolution: int = ISOSURFACE["resolution"],
+                chunk: int = ISOSURFACE["chunk"], threshold: float = ISOSURFACE["threshold"]) -> Dict[str, torch.Tensor]:
+    """one pass of BaseImplicitGeometry.isosurface_ over the box [vmin, vmax] (float32 [3] host tensors)."""
+    level = level_grid(geometry, resolution, vmin, vmax, chunk)
+    return marching_cubes(level, threshold, vmin.tolist(), vmax.tolist())
+
+
+@torch.no_grad()
+def isosurface(geometry, resolution: int = ISOSURFACE["resolution"], chunk: int = ISOSURFACE["chunk"],
+               threshold: float = ISOSURFACE["threshold"]) -> Dict[str, torch.Tensor]:
+    """BaseImplicitGeometry.isosurface: the fine-pass mesh {"v_pos", "t_pos_idx"} on the geometry's device.  geometry.bbox is the
+    deformer's canonical bbox (prepare_bbox).  Raises ValueError when the coarse pass finds no surface."""
+    bbox = geometry.bbox.detach().float().cpu()
+    coarse = isosurface_(geometry, bbox[0], bbox[1], resolution, chunk, threshold)
+    if coarse["v_pos"].shape[0] == 0:
+        raise ValueError("isosurface: the coarse pass found no surface inside the bbox")
+    ext = torch.stack([coarse["v_pos"].amin(dim=0), coarse["v_pos"].amax(dim=0)]).cpu()     # 6 floats, reduced on the device
+    del coarse
+    vmin_, vmax_ = fine_bbox(ext[0], ext[1], bbox)
+    return isosurface_(geometry, vmin_, vmax_, resolution, chunk, threshold)
+
+
+@torch.no_grad()
+def export(geometry, export_config=None) -> Dict[str, torch.Tensor]:
+    """IntrinsicAvatar.export: geometry.isosurface().  export_config (`export_vertex_color`, `chunk_size`) is accepted and changes nothing:
+    the reference computes vertex features for export_vertex_color, then attaches no colour (its v_rgb lines are commented out), so the
+    mesh is v_pos + t_pos_idx either way."""
+    return geometry.isosurface()
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m intrinsicavatar_amd.mesh",
+                                 description="canonical-space mesh (.obj) of the SDF of a reference-layout checkpoint")
+    ap.add_argument("--state-dict", required=True, help="Lightning checkpoint ({'state_dict': ...}) or a plain state dict")
+    ap.add_argument("--bbox", required=True, type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                    help="canonical bbox of the deformer (not part of the state dict)")
+    ap.add_argument("--resolution", type=int, default=ISOSURFACE["resolution"])
+    ap.add_argument("--chunk", type=int, default=ISOSURFACE["chunk"])
+    ap.add_argument("--threshold", type=float, default=ISOSURFACE["threshold"])
+    ap.add_argument("--global-step", type=int, default=25000, help="step of the progressive hash-level mask")
+    ap.add_argument("--prefix", default="model.")
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--out", required=True)
+    a = ap.parse_args(argv)
+    from . import checkpoint, fields, io_formats
+    ck = torch.load(a.state_dict, map_location="cpu", weights_only=False)       # a Lightning file also pickles its hyper-parameters
+    sd = ck.get("state_dict", ck)
+    parts = checkpoint.split_reference_state_dict(sd, a.prefix)
+    if "geometry" not in parts:
+        raise SystemExit(f"{a.state_dict}: no '{a.prefix}geometry.*' entries")
+    geo = fields.VolumeSDF(seed=None)
+    geo.load_state_dict(parts["geometry"], strict=True)
+    geo = geo.to(a.device)
+    geo.prepare_bbox(torch.tensor(a.bbox, dtype=torch.float32).view(2, 3).to(a.device))
+    geo.update_step(0, a.global_step)
+    mesh = isosurface(geo, a.resolution, a.chunk, a.threshold)
+    io_formats.save_obj(a.out, mesh["v_pos"], mesh["t_pos_idx"])
+    print(f"{a.out}: {mesh['v_pos'].shape[0]} vertices, {mesh['t_pos_idx'].shape[0]} faces")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
