@@ -758,6 +758,42 @@ int ia_mc_emit(int nx, int ny, int nz, const float* level, float threshold, cons
 int ia_mc_grid_points(int64_t n, int64_t start, int nx, int ny, int nz, const float* axes, const float* center, const float* scale,
                       float* out, ia_stream_t stream);
 
+/* ------------------------------------------------------------------------- */
+/* Frame evaluation (csrc/metrics.hip): systems/criterions.py:43-102 (PSNR, NormalError, SSIM), models/utils.py:268-277
+ * (compute_albedo_rescale_factor), systems/intrinsic_avatar.py:303-315 (transform_normals) and :396-399 (the aligned albedo).
+ * Results stay on the device; nothing synchronises.  Reductions are deterministic (fixed slices, fixed LDS tree, one final workgroup;
+ * no floating-point atomics) and accumulate in fp64.  mask: one byte per row (0 = out), NULL = every row.  tmp: ia_metric_tmp_bytes()
+ * bytes (ia_metric_ssim_tmp_bytes(H, W, C) for ia_metric_ssim), private to the call until the stream has run it.  A value that
+ * cannot be formed carries a status next to it (0 = ok) and is NaN.
+ *
+ * ia_metric_sq_err: a, b [n,C] -> sums [2] = (sum (a - b)^2 over the kept rows, number of elements summed); psnr (may be NULL) [2] =
+ *   (-10 log10(sum / count) rounded to fp32, status: 1 = no row kept).
+ * ia_metric_albedo_sums: gt, pred [n,3] -> sums [3,2] = per channel (sum gt * pred, sum pred * pred); ratio (may be NULL) [4] = the three
+ *   quotients rounded to fp32, status (1 = no row kept).
+ * ia_metric_albedo_apply: out [n,3] = mask ? clamp(ratio[c] * pred, 0, 1) : 0; ratio [3] on the device.
+ * ia_metric_transform_normals: out [n,3] = (normals @ w2c_rot^T) * (1, -1, -1); w2c_rot [3,3] row-major on the device, NULL = flip only.
+ * ia_metric_normal_error: NormalError.forward.  transform = 1: pred goes through ia_metric_transform_normals first (cam_out [n,3], may be
+ *   NULL, receives that map); normalize = 1: F.normalize (eps 1e-12) on both sides; cos = <a,b> / (|a| |b| + 1e-8), acos(clamp), degrees,
+ *   x mask -- per pixel in fp32 like the reference; err_map [n] may be NULL; sums [2] = (sum error, sum mask); result (may be NULL) [2] =
+ *   (mean rounded to fp32, status: 1 = empty mask).
+ * ia_metric_mask_rect: rect [4] int32 = (x, y, w, h) of the non-zero bytes of mask [H,W]; (0, 0, 0, 0) when there is none.
+ * ia_metric_ssim: mean SSIM of a, b [H,W,C] fp32 over rect [4] int32 ON THE DEVICE (NULL = the whole image) as scikit-image 0.18.1's
+ *   structural_similarity(multichannel=True) defines it for float input: uniform 7 x 7 window, sample covariance, K1 0.01, K2 0.03,
+ *   data_range 2, fp64, only the windows wholly inside the rectangle, channels averaged.  out [2] fp64 = (value, status: 1 = a side of the
+ *   rectangle < 7, 2 = rectangle not inside the image). */
+int64_t ia_metric_tmp_bytes(void);
+int ia_metric_sq_err(int64_t n, int C, const float* a, const float* b, const uint8_t* mask, void* tmp, double* sums, float* psnr,
+                     ia_stream_t stream);
+int ia_metric_albedo_sums(int64_t n, const float* gt, const float* pred, const uint8_t* mask, void* tmp, double* sums, float* ratio,
+                          ia_stream_t stream);
+int ia_metric_albedo_apply(int64_t n, const float* pred, const uint8_t* mask, const float* ratio, float* out, ia_stream_t stream);
+int ia_metric_transform_normals(int64_t n, const float* normals, const float* w2c_rot, float* out, ia_stream_t stream);
+int ia_metric_normal_error(int64_t n, const float* pred, const float* target, const uint8_t* mask, const float* w2c_rot, int transform,
+                           int normalize, float* cam_out, float* err_map, void* tmp, double* sums, float* result, ia_stream_t stream);
+int ia_metric_mask_rect(int H, int W, const uint8_t* mask, void* tmp, int32_t* rect, ia_stream_t stream);
+int64_t ia_metric_ssim_tmp_bytes(int H, int W, int C);
+int ia_metric_ssim(int H, int W, int C, const float* a, const float* b, const int32_t* rect, void* tmp, double* out, ia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ SOURCES = {
     "optim.hip": ["-ffp-contract=off"],
     "stepops.hip": ["-ffp-contract=off"],
     "mcubes.hip": ["-ffp-contract=off"],
+    "metrics.hip": ["-ffp-contract=off"],
 }
 
 

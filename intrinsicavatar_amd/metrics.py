@@ -1,0 +1,246 @@
+"""Frame evaluation on the device (csrc/metrics.hip): what the reference computes between "the model returned its maps" and "a number
+is logged" -- systems/criterions.py:43-102, models/utils.py:268-277, systems/intrinsic_avatar.py:303-315 and :380-399.
+
+    PSNR()(inputs, targets, valid_mask=None)                 -10 log10(mean((inputs - targets)^2 [valid_mask]))        0-d float32
+    SSIM()(inputs, targets, valid_mask=None)                 scikit-image 0.18.1's structural_similarity(multichannel=True) of two
+                                                             [H,W,C] images, cropped to the mask's bounding rectangle  0-d float64
+    NormalError()(inputs, targets, valid_mask)               mean angle in degrees over the mask                       0-d float32
+    compute_albedo_rescale_factor(gt, pred, mask)            per channel sum(gt pred) / sum(pred pred) over the mask   [3] float32
+    align_albedo(gt, pred, mask, ratio=None)                 mask ? clamp(ratio pred, 0, 1) : 0                        [n,3] float32
+    transform_normals(normals, w2c=None)                     world -> OpenGL camera space                              [n,3] float32
+    mask_rect(mask)                                          cv2.boundingRect of an [H,W] mask                         [4] int32
+
+Inputs are GPU tensors (CPU tensors raise: there is no host route); results are DEVICE tensors and nothing is read back until the
+caller converts one.  A value that cannot be formed -- an empty mask, a rectangle with a side shorter than the 7-pixel window -- is
+NaN on the device and carries a status word next to it: `.item()`, `float()`, `.tolist()` and `.cpu()` of the returned MetricValue
+read value and status in ONE copy and raise ValueError then; to_host() does so for a whole dict of metrics with one copy in all.
+Every reduction is deterministic (DESIGN.md "Frame evaluation").  LPIPS is not provided."""
+import ctypes as C
+from typing import Dict, Optional
+
+import torch
+from torch import Tensor
+
+from . import _lib as L
+
+_STATUS = {1: "nothing to average: the mask is empty, or a side of the rectangle is shorter than the 7-pixel SSIM window",
+           2: "the rectangle does not lie inside the image"}
+
+
+class MetricValue(Tensor):
+    """a device tensor that is a view of `_buf` = (value..., status): converting it to a host number checks the status."""
+
+    @staticmethod
+    def make(buf: Tensor, n_values: int, what: str) -> "MetricValue":
+        v = (buf[0] if n_values == 1 else buf[:n_values]).as_subclass(MetricValue)
+        v._buf, v._what = buf, what
+        return v
+
+    def checked(self) -> Tensor:
+        """the value on the HOST (plain tensor) after one copy of (value, status); ValueError if it could not be formed."""
+        buf = getattr(self, "_buf", None)
+        if buf is None:                                  # a tensor derived from a metric: an ordinary tensor
+            return self.as_subclass(Tensor).cpu()
+        host = buf.as_subclass(Tensor).cpu()
+        _raise_on_status(int(host[-1]), self._what)
+        return host[0] if self.dim() == 0 else host[:-1]
+
+    def item(self):
+        return self.checked().item()
+
+    def tolist(self):
+        return self.checked().tolist()
+
+    def cpu(self, *a, **k):
+        return self.checked()
+
+    def __float__(self):
+        return float(self.checked())
+
+
+def _raise_on_status(status: int, what: str):
+    if status != 0:
+        raise ValueError(f"{what}: {_STATUS.get(status, f'status {status}')}")
+
+
+def to_host(metrics: Dict[str, Tensor]) -> Dict[str, float]:
+    """every metric of a dict as a Python float (lists for vectors) with ONE device-to-host copy; ValueError on a bad status."""
+    bufs = {k: getattr(v, "_buf", None) for k, v in metrics.items()}
+    parts = [(b if b is not None else metrics[k].reshape(-1)).as_subclass(Tensor).double().reshape(-1) for k, b in bufs.items()]
+    host = torch.cat(parts).cpu() if parts else torch.zeros(0)
+    out, o = {}, 0
+    for (k, b), p in zip(bufs.items(), parts):
+        vals = host[o:o + p.numel()]
+        o += p.numel()
+        if b is not None:
+            _raise_on_status(int(vals[-1]), k)
+            vals = vals[:-1]
+        out[k] = float(vals[0]) if metrics[k].dim() == 0 else vals.tolist()
+    return out
+
+
+def _f32(t: Tensor, what: str) -> Tensor:
+    if not isinstance(t, Tensor) or not t.is_cuda:
+        raise L.IaError(f"{what}: intrinsicavatar_amd.metrics needs GPU tensors (no CPU fallback)")
+    return t.detach().as_subclass(Tensor).float().contiguous()
+
+
+def _mask(m: Optional[Tensor], n: int, what: str) -> Optional[Tensor]:
+    if m is None:
+        return None
+    if not m.is_cuda:
+        raise L.IaError(f"{what}: intrinsicavatar_amd.metrics needs GPU tensors (no CPU fallback)")
+    if m.numel() != n:
+        raise ValueError(f"{what}: the mask has {m.numel()} entries for {n} rows")
+    m = m.detach().reshape(-1)
+    return (m if m.dtype == torch.bool else m != 0).contiguous().view(torch.uint8)
+
+
+def _tmp(dev) -> Tensor:
+    return torch.empty(int(L.lib().ia_metric_tmp_bytes()), dtype=torch.uint8, device=dev)
+
+
+def squared_error(inputs: Tensor, targets: Tensor, valid_mask: Optional[Tensor] = None):
+    """-> (sums [2] float64 on the device = (sum of squared differences, number of elements), psnr MetricValue).  valid_mask selects
+    along the leading dimensions it covers, as `value[valid_mask]` does."""
+    a, b = _f32(inputs, "PSNR"), _f32(targets, "PSNR")
+    if a.shape != b.shape:
+        raise ValueError(f"PSNR: shapes differ: {tuple(a.shape)} and {tuple(b.shape)}")
+    if valid_mask is not None:
+        n = valid_mask.numel()
+        if n == 0 or a.numel() % n or tuple(a.shape[:valid_mask.dim()]) != tuple(valid_mask.shape):
+            raise ValueError(f"PSNR: a mask of shape {tuple(valid_mask.shape)} does not index maps of shape {tuple(a.shape)}")
+        c = a.numel() // n
+    else:
+        n, c = a.numel(), 1
+    dev = a.device
+    sums = torch.empty(2, dtype=torch.float64, device=dev)
+    buf = torch.empty(2, dtype=torch.float32, device=dev)
+    L.check(L.lib().ia_metric_sq_err(L.i64(n), L.i32(c), L.ptr(a), L.ptr(b), L.ptr(_mask(valid_mask, n, "PSNR")), L.ptr(_tmp(dev)),
+                                     L.ptr(sums), L.ptr(buf), L.stream()), "ia_metric_sq_err")
+    return sums, MetricValue.make(buf, 1, "PSNR")
+
+
+class PSNR(torch.nn.Module):
+    def forward(self, inputs, targets, valid_mask=None, reduction="mean"):
+        assert reduction in ["mean", "none"]
+        if reduction == "none":
+            raise NotImplementedError("PSNR(reduction='none') is not provided: no call site of the reference uses it")
+        return squared_error(inputs, targets, valid_mask)[1]
+
+
+def normal_error(inputs: Tensor, targets: Tensor, valid_mask: Optional[Tensor], *, w2c: Optional[Tensor] = None, transform: bool = False,
+                 normalize: bool = False, want_map: bool = False, want_camera: bool = False):
+    """NormalError.forward with the steps in front of it fused on request: transform (transform_normals of `inputs`, with w2c when
+    given), normalize (F.normalize on both sides).  -> dict(mean=MetricValue, sums=[2] float64 (sum error, sum mask),
+    map=[...] float32 per-pixel degrees x mask (want_map), camera=[n,3] the transformed, un-normalised inputs (want_camera))."""
+    a, b = _f32(inputs, "NormalError"), _f32(targets, "NormalError")
+    if a.shape != b.shape or a.shape[-1] != 3:
+        raise ValueError(f"NormalError: needs two [..., 3] maps of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    n, dev = a.numel() // 3, a.device
+    rot = _rotation(w2c) if transform else None
+    sums = torch.empty(2, dtype=torch.float64, device=dev)
+    buf = torch.empty(2, dtype=torch.float32, device=dev)
+    err = torch.empty(a.shape[:-1], dtype=torch.float32, device=dev) if want_map else None
+    cam = torch.empty_like(a) if (want_camera and transform) else None
+    L.check(L.lib().ia_metric_normal_error(L.i64(n), L.ptr(a), L.ptr(b), L.ptr(_mask(valid_mask, n, "NormalError")), L.ptr(rot),
+                                           L.i32(int(transform)), L.i32(int(normalize)), L.ptr(cam), L.ptr(err), L.ptr(_tmp(dev)),
+                                           L.ptr(sums), L.ptr(buf), L.stream()), "ia_metric_normal_error")
+    return dict(mean=MetricValue.make(buf, 1, "NormalError"), sums=sums, map=err, camera=cam)
+
+
+class NormalError(torch.nn.Module):
+    def forward(self, inputs, targets, valid_mask, reduction="mean"):
+        assert reduction in ["mean", "none"]
+        r = normal_error(inputs, targets, valid_mask, want_map=reduction == "none")
+        return r["mean"] if reduction == "mean" else r["map"]
+
+
+def _rotation(w2c: Optional[Tensor]) -> Optional[Tensor]:
+    """the [3,3] block transform_normals multiplies by, from a [1,4,4] / [4,4] / [3,3] world-to-camera matrix."""
+    if w2c is None:
+        return None
+    if not w2c.is_cuda:
+        raise L.IaError("transform_normals: intrinsicavatar_amd.metrics needs GPU tensors (no CPU fallback)")
+    if w2c.dim() == 3:
+        assert w2c.shape[0] == 1 and w2c.shape[1] == 4 and w2c.shape[2] == 4
+        w2c = w2c[0]
+    return w2c[:3, :3].detach().float().contiguous()
+
+
+def transform_normals(normals: Tensor, w2c: Optional[Tensor] = None) -> Tensor:
+    """world-space normal map -> OpenGL camera space: normals @ w2c[:3,:3]^T when w2c is given, then x (1, -1, -1)."""
+    a = _f32(normals, "transform_normals")
+    if a.shape[-1] != 3:
+        raise ValueError(f"transform_normals: needs a [..., 3] map, got {tuple(a.shape)}")
+    out = torch.empty_like(a)
+    L.check(L.lib().ia_metric_transform_normals(L.i64(a.numel() // 3), L.ptr(a), L.ptr(_rotation(w2c)), L.ptr(out), L.stream()),
+            "ia_metric_transform_normals")
+    return out
+
+
+def albedo_sums(gt_albedo: Tensor, pred_albedo: Tensor, gt_mask: Optional[Tensor]):
+    """-> (sums [3,2] float64 on the device = per channel (sum gt pred, sum pred pred) over the mask, ratio MetricValue [3] float32)."""
+    x, xh = _f32(gt_albedo, "compute_albedo_rescale_factor"), _f32(pred_albedo, "compute_albedo_rescale_factor")
+    if x.shape != xh.shape or x.shape[-1] != 3:
+        raise ValueError(f"compute_albedo_rescale_factor: needs two [..., 3] maps of one shape, got {tuple(x.shape)} and {tuple(xh.shape)}")
+    n, dev = x.numel() // 3, x.device
+    sums = torch.empty((3, 2), dtype=torch.float64, device=dev)
+    buf = torch.empty(4, dtype=torch.float32, device=dev)
+    L.check(L.lib().ia_metric_albedo_sums(L.i64(n), L.ptr(x), L.ptr(xh), L.ptr(_mask(gt_mask, n, "compute_albedo_rescale_factor")),
+                                          L.ptr(_tmp(dev)), L.ptr(sums), L.ptr(buf), L.stream()), "ia_metric_albedo_sums")
+    return sums, MetricValue.make(buf, 3, "compute_albedo_rescale_factor")
+
+
+def compute_albedo_rescale_factor(gt_albedo: Tensor, pred_albedo: Tensor, gt_mask: Tensor) -> Tensor:
+    return albedo_sums(gt_albedo, pred_albedo, gt_mask)[1]
+
+
+def align_albedo(gt_albedo: Tensor, pred_albedo: Tensor, gt_mask: Tensor, ratio: Optional[Tensor] = None):
+    """the reference's three_aligned_albedo: zeros_like(gt), and on the mask clamp(ratio * pred, 0, 1); the ratio is computed from
+    (gt, pred, mask) when it is not given.  -> (aligned [n,3] float32, ratio [3])."""
+    if ratio is None:
+        ratio = compute_albedo_rescale_factor(gt_albedo, pred_albedo, gt_mask)
+    xh = _f32(pred_albedo, "align_albedo")
+    n = xh.numel() // 3
+    out = torch.empty_like(xh)
+    L.check(L.lib().ia_metric_albedo_apply(L.i64(n), L.ptr(xh), L.ptr(_mask(gt_mask, n, "align_albedo")), L.ptr(_f32(ratio, "align_albedo")),
+                                           L.ptr(out), L.stream()), "ia_metric_albedo_apply")
+    return out, ratio
+
+
+def mask_rect(mask: Tensor) -> Tensor:
+    """(x, y, w, h) int32 on the device of the non-zero pixels of an [H,W] mask -- cv2.boundingRect; (0, 0, 0, 0) when there is none."""
+    if mask.dim() != 2:
+        raise ValueError(f"mask_rect: needs an [H, W] mask, got {tuple(mask.shape)}")
+    H, W = (int(s) for s in mask.shape)
+    m = _mask(mask, H * W, "mask_rect")
+    rect = torch.empty(4, dtype=torch.int32, device=mask.device)
+    L.check(L.lib().ia_metric_mask_rect(L.i32(H), L.i32(W), L.ptr(m), L.ptr(_tmp(mask.device)), L.ptr(rect), L.stream()), "ia_metric_mask_rect")
+    return rect
+
+
+def ssim(inputs: Tensor, targets: Tensor, rect: Optional[Tensor] = None) -> MetricValue:
+    """mean SSIM of two [H,W,C] images over rect = (x, y, w, h) int32 ON THE DEVICE (None: the whole image); 0-d float64."""
+    a, b = _f32(inputs, "SSIM"), _f32(targets, "SSIM")
+    if a.shape != b.shape or a.dim() != 3:
+        raise ValueError(f"SSIM: needs two [H, W, C] images of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    H, W, Cn = (int(s) for s in a.shape)
+    if rect is not None:
+        if not rect.is_cuda or rect.dtype != torch.int32 or rect.numel() != 4:
+            raise ValueError("SSIM: rect must be 4 int32 values on the device (mask_rect's output)")
+        rect = rect.contiguous()
+    lib, dev = L.lib(), a.device
+    tmp = torch.empty(int(lib.ia_metric_ssim_tmp_bytes(L.i32(H), L.i32(W), L.i32(Cn))), dtype=torch.uint8, device=dev)
+    buf = torch.empty(2, dtype=torch.float64, device=dev)
+    L.check(lib.ia_metric_ssim(L.i32(H), L.i32(W), L.i32(Cn), L.ptr(a), L.ptr(b), L.ptr(rect), L.ptr(tmp), L.ptr(buf), L.stream()), "ia_metric_ssim")
+    return MetricValue.make(buf, 1, "SSIM")
+
+
+class SSIM(torch.nn.Module):
+    def forward(self, inputs, targets, valid_mask=None):
+        rect = None
+        if valid_mask is not None:
+            assert valid_mask.dtype == torch.bool
+            rect = mask_rect(valid_mask)
+        return ssim(inputs, targets, rect)

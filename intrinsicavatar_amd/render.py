@@ -515,11 +515,14 @@ class RenderStep:
     def relight(self, rays: Tensor, material, emitter, spp: int, light_u: Tensor, shuffle_u: Tensor,
                 background_color: Optional[Tensor] = None, global_illumination: bool = False,
                 jitter: Optional[Tensor] = None, render_mode: str = "light", scatter_u: Optional[Tensor] = None,
-                return_index_lists: bool = False) -> Dict[str, Tensor]:
+                return_index_lists: bool = False, albedo_only: bool = False, albedo_align_ratio: Optional[Tensor] = None) -> Dict[str, Tensor]:
         """forward_ with enable_phys and render_mode='light' (BASELINE configs 3 / 5):
         rendering_with_normals_mats_sdf (volrend.py:810-1020) -> sample_volume_interaction (pbr/utils.py:70-229)
         -> per-ray shuffled light directions (:1356-1378) -> secondary rays (:396-545) -> pbr_light_forward (:755-861)
-        -> accumulate(resampled_weights, Lo) (:1427-1466).  light_u [spp,3], shuffle_u [n_rays,spp]: explicit RNG."""
+        -> accumulate(resampled_weights, Lo) (:1427-1466).  light_u [spp,3], shuffle_u [n_rays,spp]: explicit RNG.
+        albedo_align_ratio [3]: the material head's albedo is multiplied by it before it is composited AND before it is shaded
+        (:1114-1115).  albedo_only (:222, :1290): the primary samples are shaded and composited, the volume-interaction / secondary-ray
+        branch is skipped -- comp_rgb_phys = comp_demod_phys = the background colour on every ray."""
         from . import pbr
         dfm = self.deformer
         rays_o, rays_d, far, t_starts, t_ends, ray_indices, packed_info, stats = self.sample(rays, jitter)
@@ -536,6 +539,8 @@ class RenderStep:
         alphas = laplace_alpha_intervals(d["sdf"], t_starts, t_ends, beta)
         rgbs, enc2, xp2 = self.radiance(d["pts_cano"], d["feature"], refl01, normal_world, return_embedding=True)
         mats = material(enc2, xp2, d["feature"], self.radiance.prog.mask(self.radiance.global_step, dev))
+        if albedo_align_ratio is not None:
+            mats = torch.cat([mats[:, :3] * albedo_align_ratio.as_subclass(Tensor).to(mats).reshape(1, 3), mats[:, 3:]], dim=1)
         weights, trans = nerfacc.render_weight_from_alpha(alphas, packed_info=packed_info)
         acc = lambda v: nerfacc._Accumulate.apply(weights, v, ray_indices, packed_info)      # noqa: E731
         out = dict(comp_rgb=acc(rgbs), comp_normal=acc(normal_world), albedo=acc(mats[:, :3].contiguous()),
@@ -551,7 +556,7 @@ class RenderStep:
         if render_mode == "uniform_light":
             out["visibility"] = torch.zeros((n_rays, 1), device=dev)                      # :1266-1267
         stats.update(n_resampled=0, n_fg=0, n_secondary=0)
-        if ray_indices.numel() > 0:
+        if ray_indices.numel() > 0 and not albedo_only:
             # -- volume-interaction re-sampling (sample_volume_interaction, models/pbr/utils.py:70-229): K1 + layout scans
             vi = pbr.VolumeInteraction(ray_indices, t_starts, t_ends, n_rays, spp, weights, d["sdf"])
             stats["n_resampled"], stats["n_fg"] = vi.R, vi.F
@@ -654,13 +659,16 @@ class RenderStep:
     @torch.no_grad()
     def forward_(self, rays: Tensor, material, emitter, spp: int, light_u: Tensor, shuffle_u: Optional[Tensor] = None,
                  background_color: Optional[Tensor] = None, global_illumination: bool = False, render_mode: str = "light",
-                 scatter_u: Optional[Tensor] = None, jitter: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                 scatter_u: Optional[Tensor] = None, jitter: Optional[Tensor] = None, albedo_only: bool = False,
+                 albedo_align_ratio: Optional[Tensor] = None) -> Dict[str, Tensor]:
         """IntrinsicAvatarModel.forward_ in eval mode with enable_phys (models/intrinsic_avatar.py:950-1651): relight() + the
-        reference's output dict.  Random tensors are explicit."""
+        reference's output dict.  Random tensors are explicit.  albedo_only / albedo_align_ratio: the two model
+        switches of the reference's test step (relight())."""
         if background_color is None:
             background_color = torch.ones(3, device=rays.device)
         o = self.relight(rays, material, emitter, spp, light_u, shuffle_u, background_color=background_color,
-                         global_illumination=global_illumination, jitter=jitter, render_mode=render_mode, scatter_u=scatter_u)
+                         global_illumination=global_illumination, jitter=jitter, render_mode=render_mode, scatter_u=scatter_u,
+                         albedo_only=albedo_only, albedo_align_ratio=albedo_align_ratio)
         return self.output_dict(o, background_color, render_mode, o["stats"]["n_samples"])
 
     def forward_train_(self, rays: Tensor, material, emitter, spp: int, light_u: Optional[Tensor], jitter: Optional[Tensor] = None,

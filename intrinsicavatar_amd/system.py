@@ -6,8 +6,10 @@
     chunk_batch       models/utils.py:16-61                 run a function over slices of its batched tensor arguments, merge the results
     model_forward     models/intrinsic_avatar.py:1653-1666  IntrinsicAvatarModel.forward: forward_ as it is in training, chunk_batch over
                                                             `ray_chunk` rays with the results moved to the host in evaluation, + "beta"
+    evaluate_frame    systems/intrinsic_avatar.py:317-421,  the numeric part of validation_step / test_step: albedo-only pass -> ratio ->
+                      :597-720                              relit pass, and the frame's metrics (metrics.py: kernels, results on the device)
 
-Plain tensor plumbing on whatever device the batch lives on (no kernels: a few element-wise operators per frame); held to the reference's
+The first three are plain tensor plumbing on whatever device the batch lives on (no kernels: a few element-wise operators per frame); held to the reference's
 own functions by tests/golden/golden_system.npz (tests/golden/make_golden_system.py)."""
 from collections import defaultdict
 from typing import Callable, Dict, Optional, Tuple
@@ -15,7 +17,7 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 from torch import Tensor
 
-from . import pbr
+from . import metrics, pbr
 
 BACKGROUNDS = ("white", "black", "random")
 
@@ -106,3 +108,55 @@ def model_forward(rs, rays: Tensor, material, emitter, spp: int, light_u: Tensor
     else:
         out = chunk_batch(lambda r, su: rs.forward_(r, material, emitter, spp, light_u, su, **kw), ray_chunk, move_to_cpu, rays, shuffle_u)
     return {**out, "beta": rs.density.get_beta()}
+
+
+METRIC_KEYS = ("rf_psnr", "rf_ssim", "normal_error", "pbr_psnr", "pbr_ssim", "albedo_psnr", "albedo_ssim")      # the reference's, minus *_lpips
+
+
+def evaluate_frame(rs, batch: Dict[str, Tensor], material, emitter, spp: int, light_u: Tensor, shuffle_u: Optional[Tensor] = None, *,
+                   img_wh: Tuple[int, int], stage: str = "test", **kw) -> Tuple[Dict[str, Tensor], Dict[str, Tensor]]:
+    """the numeric part of validation_step (:317-421) / test_step (:597-720) on a batch that went through preprocess_data (device
+    tensors).  stage "test" with both "hdri" and "albedo" in the batch: an albedo-only pass, the per-channel ratio against the ground
+    truth, then the full pass with that ratio (its comp_albedo_full IS the aligned albedo, :697-698); otherwise one full pass and, if
+    "albedo" is there, the alignment afterwards (:380-399, :681-696).  -> (metrics, out): metrics under the reference's keys without
+    *_lpips, 0-d device tensors (metrics.to_host(metrics): every one of them with a single read-back); out = the model's dict on the
+    device with "comp_normal" in OpenGL camera space, + "aligned_albedo" when one was formed.  **kw goes to model_forward."""
+    assert stage in ("validation", "test")
+    W, H = img_wh
+    rays = batch["rays"]
+    kw = dict(kw, move_to_cpu=False)
+    aligned_by_model = stage == "test" and "hdri" in batch and "albedo" in batch
+    gt_albedo = batch.get("albedo")
+    gt_mask = batch["alpha"] > 0.5 if ("albedo" in batch or "normal" in batch) else None
+    ratio = None
+    if aligned_by_model:
+        pred_albedo = model_forward(rs, rays, material, emitter, spp, light_u, shuffle_u, albedo_only=True, **kw)["comp_albedo_full"]
+        ratio = metrics.compute_albedo_rescale_factor(gt_albedo, pred_albedo, gt_mask)
+    out = model_forward(rs, rays, material, emitter, spp, light_u, shuffle_u, albedo_align_ratio=ratio, **kw)
+    valid = batch.get("valid_mask")
+    psnr, ssim = metrics.PSNR(), metrics.SSIM()
+    img = lambda t: t.reshape(H, W, 3)      # noqa: E731
+    ret = {}
+    if "rgb" in batch:
+        rect = metrics.mask_rect(valid.reshape(H, W)) if valid is not None else None
+        ret["rf_psnr"] = psnr(out["comp_rgb_full"], batch["rgb"], valid_mask=valid)
+        ret["rf_ssim"] = metrics.ssim(img(out["comp_rgb_full"]), img(batch["rgb"]), rect)
+    if "normal" in batch:
+        r = metrics.normal_error(out["comp_normal"], batch["normal"], gt_mask, w2c=batch.get("w2c"), transform=True, normalize=True,
+                                 want_camera=True)
+        out["comp_normal"] = r["camera"]
+        ret["normal_error"] = r["mean"]
+    else:
+        out["comp_normal"] = metrics.transform_normals(out["comp_normal"], batch.get("w2c"))
+    if "rgb" in batch:
+        ret["pbr_psnr"] = psnr(out["comp_rgb_phys_full"], batch["rgb"], valid_mask=valid)
+        ret["pbr_ssim"] = metrics.ssim(img(out["comp_rgb_phys_full"]), img(batch["rgb"]), rect)
+    if "albedo" in batch:
+        if aligned_by_model:
+            aligned = out["comp_albedo_full"]
+        else:
+            aligned, ratio = metrics.align_albedo(gt_albedo, out["comp_albedo_full"], gt_mask)
+        out["aligned_albedo"] = aligned
+        ret["albedo_psnr"] = psnr(aligned, gt_albedo, valid_mask=gt_mask)
+        ret["albedo_ssim"] = ssim(img(aligned), img(gt_albedo), valid_mask=gt_mask.reshape(H, W))
+    return ret, out
