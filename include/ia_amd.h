@@ -794,6 +794,26 @@ int ia_metric_mask_rect(int H, int W, const uint8_t* mask, void* tmp, int32_t* r
 int64_t ia_metric_ssim_tmp_bytes(int H, int W, int C);
 int ia_metric_ssim(int H, int W, int C, const float* a, const float* b, const int32_t* rect, void* tmp, double* out, ia_stream_t stream);
 
+/* ------------------------------------------------------------------------- */
+/* Deformer construction (csrc/skinning.hip): ForwardDeformer.switch_to_explicit(use_smpl=True) + query_weights_smpl
+ * (models/deformers/fast_snarf/deformer_torch.py:139-253) on the device.  Conventions (voxel order, tie rule, summation orders):
+ * csrc/skin_math.h and DESIGN.md "Deformer construction".  None of the four needs scratch memory.
+ *
+ * ia_knn_points: p1 [P,3], p2 [V,3] fp32 -> d2 [P,K] fp32, idx [P,K] int32, 1 <= K <= 32, V >= K: the K smallest pairs under the
+ *   lexicographic order (d2, index) with d2 = ((dx*dx + dy*dy) + dz*dz), ascending in that order (pytorch3d knn_points, squared
+ *   distances; equal distances are ordered by index).  The result does not depend on P or on the launch.
+ * ia_skin_blend: d2, idx [P,K] + weights [V,24] -> out [24,P]: dist = clamp(sqrt(d2), 1e-4, 1), ws = (1 / dist) / sum_k, row =
+ *   sum_k ws_k * weights[idx_k] in ascending k.  A row with an index outside [0, V) is NaN.
+ * ia_skin_smooth: one sweep src -> dst, both [24,D,H,W] and distinct: interior voxels (w - mean) * 0.7 + mean with mean = the six face
+ *   neighbours of src (d+1, d-1, h+1, h-1, w+1, w-1, added left to right) / 6, border voxels unchanged, then every voxel / its
+ *   24-channel sum.
+ * ia_skin_grid_points: out [D*H*W,3] (W fastest) = (linspace(-1,1,W)[w], linspace(-1,1,H)[h], linspace(-1,1,D)[d] / ratio) * scale +
+ *   (ox, oy, oz), torch.linspace's float32 values, one rounding per step. */
+int ia_knn_points(int64_t P, int V, int K, const float* p1, const float* p2, float* d2, int32_t* idx, ia_stream_t stream);
+int ia_skin_blend(int64_t P, int V, int K, const float* d2, const int32_t* idx, const float* weights, float* out, ia_stream_t stream);
+int ia_skin_smooth(int D, int H, int W, const float* src, float* dst, ia_stream_t stream);
+int ia_skin_grid_points(int D, int H, int W, float ratio, float scale, float ox, float oy, float oz, float* out, ia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

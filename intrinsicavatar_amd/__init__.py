@@ -7,6 +7,7 @@ render_step hot path, exposed through the operator surface the reference imports
     intrinsicavatar_amd.tinycudann    <- `tinycudann` (Encoding: HashGrid / SphericalHarmonics, incl. double backward)
     intrinsicavatar_amd.pbr           <- `lib.torch_pbr` (emitter / scatterer classes, colour helpers) + the fused estimators and the
                                          kernels behind models/pbr/utils.py sample_volume_interaction
+    intrinsicavatar_amd.pytorch3d_ops <- `lib.pytorch3d.ops` (knn_points, knn_gather)
     intrinsicavatar_amd.volrend       <- `models/volrend.py` (rendering, rendering_with_normals_sdf, rendering_with_normals_mats_sdf)
 
 All compute runs in hand-written HIP kernels behind the C ABI of include/ia_amd.h
@@ -28,11 +29,12 @@ if _os.environ.get("IA_HOST_TUNING") == "1":
 
 def install_aliases() -> None:
     """make the reference's own import statements resolve to this package:
-    `import nerfacc`, `from nerfacc.volrend import ...`, `from lib.nerfacc import ...`, `import tinycudann as tcnn`.
+    `import nerfacc`, `from nerfacc.volrend import ...`, `from lib.nerfacc import ...`, `import tinycudann as tcnn`,
+    `from lib.pytorch3d import ops`.
     Call it before the reference's modules are imported (top of launch.py / sitecustomize.py)."""
     import sys
     import types
-    from . import lib_nerfacc, nerfacc, pbr, tinycudann
+    from . import lib_nerfacc, nerfacc, pbr, pytorch3d_ops, tinycudann
     sys.modules["nerfacc"] = nerfacc
     sys.modules["nerfacc.volrend"] = nerfacc
     lib = sys.modules.get("lib") or types.ModuleType("lib")
@@ -42,3 +44,8 @@ def install_aliases() -> None:
     lib.torch_pbr = pbr                     # the eleven classes of models/__init__.py:39-51 + rgb_to_srgb, luminance, luma, max_value
     sys.modules["lib.torch_pbr"] = pbr
     sys.modules["tinycudann"] = tinycudann
+    p3d = sys.modules.get("lib.pytorch3d") or types.ModuleType("lib.pytorch3d")      # `from lib.pytorch3d import ops` (deformer_torch.py:1)
+    p3d.ops = pytorch3d_ops
+    lib.pytorch3d = p3d
+    sys.modules["lib.pytorch3d"] = p3d
+    sys.modules["lib.pytorch3d.ops"] = pytorch3d_ops

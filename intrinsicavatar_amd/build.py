@@ -35,6 +35,7 @@ SOURCES = {
     "stepops.hip": ["-ffp-contract=off"],
     "mcubes.hip": ["-ffp-contract=off"],
     "metrics.hip": ["-ffp-contract=off"],
+    "skinning.hip": ["-ffp-contract=off"],
 }
 
 

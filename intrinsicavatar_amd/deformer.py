@@ -59,6 +59,34 @@ class SNARFDeformer:
         self.voxel_d = None
         self.w2s = None
 
+    @classmethod
+    @torch.no_grad()
+    def from_smpl(cls, smpl_verts: Tensor, smpl_weights: Tensor, resolution: int = 128, global_scale: float = 1.2) -> "SNARFDeformer":
+        """ForwardDeformer.switch_to_explicit(use_smpl=True) (deformer_torch.py:139-197): the skinning-weight grid
+        [1,24,resolution // 4,resolution,resolution] of the body surface smpl_verts [1,V,3] / smpl_weights [1,V,24] (GPU tensors), its
+        offset / scale (from the vertex bounds, z range compressed by ratio = 4) and the grid's bbox.  The six vertex bounds are read
+        back once; the scalars are formed on the host by the reference's float32 expressions."""
+        if not smpl_verts.is_cuda:
+            raise L.IaError("SNARFDeformer.from_smpl needs GPU tensors (no CPU fallback)")
+        dev = smpl_verts.device
+        verts = smpl_verts.detach().float().reshape(1, -1, 3)
+        d, h, w = resolution // 4, resolution, resolution
+        ratio = h / d
+        gt_bbox = torch.cat([verts.min(dim=1).values, verts.max(dim=1).values], dim=0).cpu()
+        offset = (gt_bbox[0] + gt_bbox[1])[None, None, :] * 0.5
+        scale = (gt_bbox[1] - gt_bbox[0]).max() / 2 * global_scale
+        corner = torch.ones_like(offset[0]) * scale
+        corner[0, 2] /= ratio
+        bbox = torch.cat([(offset - corner).reshape(1, 3), (offset + corner).reshape(1, 3)], dim=0)
+        scale_kernel = torch.zeros_like(offset)
+        scale_kernel[...] = 1. / scale
+        scale_kernel[:, :, -1] = scale_kernel[:, :, -1] * ratio
+        x = fast_snarf.skin_grid_points(d, h, w, ratio, float(scale), offset.reshape(3).tolist(), dev)
+        grid = fast_snarf.query_weights_smpl(x[None], verts, smpl_weights.detach().reshape(1, -1, 24), resolution)
+        out = cls(grid, (-offset).to(dev), scale_kernel.to(dev), bbox.to(dev))
+        out.offset, out.scale, out.resolution = offset.to(dev), scale.to(dev), resolution
+        return out
+
     @property
     def last_overflow_records(self) -> int:
         """points the early-filter kernel searched again with the filter off, in THIS thread's last _candidates call."""
@@ -423,3 +451,18 @@ class SNARFDeformer:
             L.ptr(out.get("sdf_grad")), L.ptr(out.get("sdf_grad_cano")), L.ptr(out.get("feature")), st),
             "ia_deform_select")
         return out
+
+
+@torch.no_grad()
+def initialize(body, betas: Tensor, cano_pose="da_pose", resolution: int = 128):
+    """the numeric part of SNARFDeformer.initialize (snarf_deformer.py:46-79): the body (smpl.SMPLKinematics) in its canonical pose
+    -> (deformer, A_rest_inv [1,J,4,4] float32, bbox [2,3] = get_bbox_from_smpl of the canonical vertices, vs_template [1,V,3]).
+    Per frame the caller goes on with smpl.deformer_transforms(A, A_rest_inv) and deformer.prepare(tfs, w2s)."""
+    from . import smpl
+    dev = body.v_template.device
+    body_pose_t = smpl.rest_pose(cano_pose, device=dev).to(body.v_template.dtype)
+    out = body.forward(betas[:1].to(body.v_template.dtype), body_pose_t, torch.zeros((1, 3), dtype=body.v_template.dtype, device=dev))
+    A_rest_inv = torch.linalg.inv(out["A"].float())
+    vs_template = out["vertices"]
+    deformer = SNARFDeformer.from_smpl(vs_template.float(), body.lbs_weights[None].float(), resolution=resolution)
+    return deformer, A_rest_inv, smpl.bbox_from_vertices(vs_template), vs_template

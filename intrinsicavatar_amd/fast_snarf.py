@@ -169,3 +169,59 @@ def filter(x: Tensor, mask: Tensor) -> Tensor:
     out = torch.empty_like(mask)
     L.check(L.lib().ia_filter(L.i64(N), L.i32(I), L.ptr(x), L.ptr(mask), L.ptr(out), L.stream()), "ia_filter")
     return out
+
+
+# -- building the skinning-weight grid from a body surface (deformer_torch.py:139-253; csrc/skinning.hip) --------------------------
+SMOOTH_SWEEPS = 30        # deformer_torch.py:246
+KNN_K = 30                # deformer_torch.py:236
+
+
+def skin_grid_points(D: int, H: int, W: int, ratio: float, scale: float, offset, device) -> Tensor:
+    """voxel centres [D*H*W,3] of switch_to_explicit (deformer_torch.py:145-186): linspace(-1, 1) per axis, z / ratio, * scale, + offset."""
+    out = torch.empty((D * H * W, 3), dtype=torch.float32, device=device)
+    ox, oy, oz = (float(v) for v in offset)
+    L.check(L.lib().ia_skin_grid_points(L.i32(D), L.i32(H), L.i32(W), L.f32(ratio), L.f32(scale), L.f32(ox), L.f32(oy), L.f32(oz),
+                                        L.ptr(out), L.stream()), "ia_skin_grid_points")
+    return out
+
+
+def skin_blend(d2: Tensor, idx: Tensor, weights: Tensor) -> Tensor:
+    """d2 [P,K] fp32, idx [P,K] int32, weights [V,24] -> [24,P]: the inverse-distance blend of query_weights_smpl (:237-242)."""
+    P, K = d2.shape
+    if idx.dtype != torch.int32 or idx.shape != d2.shape or weights.dim() != 2 or weights.shape[1] != 24:
+        raise RuntimeError("skin_blend: d2 [P,K] fp32, idx [P,K] int32, weights [V,24]")
+    out = torch.empty((24, P), dtype=torch.float32, device=d2.device)
+    L.check(L.lib().ia_skin_blend(L.i64(P), L.i32(weights.shape[0]), L.i32(K), L.ptr(d2.contiguous().float()), L.ptr(idx.contiguous()),
+                                  L.ptr(weights.contiguous().float()), L.ptr(out), L.stream()), "ia_skin_blend")
+    return out
+
+
+def skin_smooth(weights: Tensor, sweeps: int = SMOOTH_SWEEPS) -> Tensor:
+    """`sweeps` sweeps of deformer_torch.py:246-252 on a [24,D,H,W] grid (two buffers, ping-pong); returns the smoothed grid."""
+    if weights.dim() != 4 or weights.shape[0] != 24:
+        raise RuntimeError("skin_smooth: weights [24,D,H,W]")
+    _, D, H, W = weights.shape
+    a = weights.contiguous().float()
+    if sweeps == 0:
+        return a
+    if a.data_ptr() == weights.data_ptr():
+        a = a.clone()                                    # the caller's tensor is not written
+    b = torch.empty_like(a)
+    for _ in range(sweeps):
+        L.check(L.lib().ia_skin_smooth(L.i32(D), L.i32(H), L.i32(W), L.ptr(a), L.ptr(b), L.stream()), "ia_skin_smooth")
+        a, b = b, a
+    return a
+
+
+def query_weights_smpl(x: Tensor, smpl_verts: Tensor, smpl_weights: Tensor, resolution: int = 128) -> Tensor:
+    """query_weights_smpl (deformer_torch.py:234-253): x [1,P,3] with P = (resolution // 4) * resolution^2 voxel centres, smpl_verts
+    [1,V,3], smpl_weights [1,V,24] -> [1,24,resolution // 4,resolution,resolution]."""
+    from . import pytorch3d_ops
+    d, h, w = resolution // 4, resolution, resolution
+    if x.dim() != 3 or x.shape[0] != 1 or x.shape[1] != d * h * w:
+        raise ValueError(f"query_weights_smpl: x must be [1, {d * h * w}, 3] for resolution {resolution}, got {tuple(x.shape)}")
+    if not x.is_cuda:
+        raise L.IaError("query_weights_smpl needs GPU tensors (no CPU fallback)")
+    d2, idx = pytorch3d_ops.knn_points_flat(x[0].detach().contiguous().float(), smpl_verts[0].detach().contiguous().float(), KNN_K)
+    blend = skin_blend(d2, idx, smpl_weights[0].detach())
+    return skin_smooth(blend.view(24, d, h, w), SMOOTH_SWEEPS)[None]

@@ -12,6 +12,7 @@ call reads back its two output sizes once, isosurface() additionally the coarse 
 extraction: csrc/mc_math.h and DESIGN.md "Mesh export".
 
     python -m intrinsicavatar_amd.mesh --state-dict CKPT --bbox x0 y0 z0 x1 y1 z1 [--resolution 512] [--global-step 25000] --out mesh.obj
+    python -m intrinsicavatar_amd.mesh --state-dict CKPT --smpl-npz BODY.npz [--cano-pose A_pose] ... --out mesh.obj
 """
 import argparse
 import ctypes as C
@@ -127,12 +128,34 @@ def export(geometry, export_config=None) -> Dict[str, torch.Tensor]:
     return geometry.isosurface()
 
 
+def smpl_npz_bbox(path: str, cano_pose="A_pose") -> torch.Tensor:
+    """[2,3] float32 canonical bbox of the body stored in an .npz (the arrays smpl.SMPLKinematics takes, plus betas): the body in its
+    canonical pose, then smpl.bbox_from_vertices (SNARFDeformer.initialize, snarf_deformer.py:46-71).  24 joints on the host."""
+    import numpy as np
+    from . import smpl
+    z = np.load(path)
+    missing = [k for k in ("v_template", "shapedirs", "posedirs", "J_regressor", "parents", "lbs_weights", "betas") if k not in z.files]
+    if missing:
+        raise SystemExit(f"{path}: missing arrays {missing}")
+    t = lambda k: torch.from_numpy(np.asarray(z[k], dtype=np.float64))      # noqa: E731
+    body = smpl.SMPLKinematics(t("v_template"), t("shapedirs"), t("posedirs"), t("J_regressor"), z["parents"].tolist(), t("lbs_weights"))
+    if isinstance(cano_pose, str) and "," in cano_pose:
+        cano_pose = [float(v) for v in cano_pose.split(",")]
+    betas = t("betas").reshape(-1, body.shapedirs.shape[-1])[:1]
+    out = body.forward(betas, smpl.rest_pose(cano_pose).double(), torch.zeros((1, 3), dtype=torch.float64))
+    return smpl.bbox_from_vertices(out["vertices"].float())
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m intrinsicavatar_amd.mesh",
                                  description="canonical-space mesh (.obj) of the SDF of a reference-layout checkpoint")
     ap.add_argument("--state-dict", required=True, help="Lightning checkpoint ({'state_dict': ...}) or a plain state dict")
-    ap.add_argument("--bbox", required=True, type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
-                    help="canonical bbox of the deformer (not part of the state dict)")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--bbox", type=float, nargs=6, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                     help="canonical bbox of the deformer (not part of the state dict)")
+    src.add_argument("--smpl-npz", metavar="FILE", help="body model arrays (v_template, shapedirs, posedirs, J_regressor, parents, "
+                     "lbs_weights) plus betas: the bbox is that of the body in its canonical pose (smpl.bbox_from_vertices)")
+    ap.add_argument("--cano-pose", default="A_pose", help="canonical pose of --smpl-npz: a predefined name or four comma-separated numbers")
     ap.add_argument("--resolution", type=int, default=ISOSURFACE["resolution"])
     ap.add_argument("--chunk", type=int, default=ISOSURFACE["chunk"])
     ap.add_argument("--threshold", type=float, default=ISOSURFACE["threshold"])
@@ -150,7 +173,8 @@ def main(argv=None) -> int:
     geo = fields.VolumeSDF(seed=None)
     geo.load_state_dict(parts["geometry"], strict=True)
     geo = geo.to(a.device)
-    geo.prepare_bbox(torch.tensor(a.bbox, dtype=torch.float32).view(2, 3).to(a.device))
+    bbox = torch.tensor(a.bbox, dtype=torch.float32).view(2, 3) if a.bbox is not None else smpl_npz_bbox(a.smpl_npz, a.cano_pose)
+    geo.prepare_bbox(bbox.to(a.device))
     geo.update_step(0, a.global_step)
     mesh = isosurface(geo, a.resolution, a.chunk, a.threshold)
     io_formats.save_obj(a.out, mesh["v_pos"], mesh["t_pos_idx"])
