@@ -814,6 +814,39 @@ int ia_skin_blend(int64_t P, int V, int K, const float* d2, const int32_t* idx, 
 int ia_skin_smooth(int D, int H, int W, const float* src, float* dst, ia_stream_t stream);
 int ia_skin_grid_points(int D, int H, int W, float ratio, float scale, float ox, float oy, float oz, float* out, ia_stream_t stream);
 
+/* ------------------------------------------------------------------------- */
+/* Training batches (csrc/data.hip): make_rays and PeopleSnapshotDataset.__getitem__ (datasets/peoplesnapshot.py:19-33, :119-175) with
+ * EdgeSampler / UniformSampler (utils/sampler.py:9-67) on frames resident on the device.  Conventions (fp64 ray arithmetic, window
+ * offsets, the draw rule): csrc/data_math.h and DESIGN.md "Training batches".  A pixel is its row-major index p = y * W + x.
+ * cam_host (HOST [21] fp64): inv(K) row-major [9], c2w[:3,:3] row-major [9], c2w[:3,3] [3].
+ *
+ * ia_make_rays: rays_o, rays_d [n,3] fp32 of the pixels in `pixels` [n] int64 (NULL: pixel j of row j, n <= H * W).  A pixel outside
+ *   the frame gives zeros.
+ * ia_window_minmax: in [outer,len,inner] fp32 -> out_min, out_max (same shape, either may be NULL, neither may be `in`): minimum and
+ *   maximum over the k taps at offsets -(k/2) ... k - 1 - k/2 along `len`, taps outside the array ignored; 1 <= k <= 64.
+ * ia_flag_lists_count / _fill: mask, mask_i, mask_o [F,N] fp32 -> the ascending pixel lists of (mask != 0) and (mask_o - mask_i != 0) of
+ *   every frame as CSR: mask_start, edge_start [F+1], counts [F,2] = (mask, edge) sizes, mask_loc, edge_loc (pixel inside its frame),
+ *   all int32; F * N < 2^31.  count leaves totals [2] int32 on the device = the lengths of mask_loc and edge_loc, which the caller reads to
+ *   allocate them (an empty list may be NULL); scratch: ia_flag_lists_scratch_bytes(F, N) bytes, handed on unchanged to fill.
+ * ia_sample_batch: n rows of frame `frame` of masks [F,H*W] fp32 / images [F,H*W,3] u8.  Pixel of row j: mask_loc[frame][w_j % n_mask]
+ *   for j < num_mask, edge_loc[frame][w_j % n_edge] for the next num_edge rows, w_j % (H * W) for the rest, with words [n] int64 >= 0
+ *   (the sign bit is ignored); words NULL (num_mask = num_edge = 0, n <= H * W): pixel j.  Outputs: indices [n] int64, alpha [n] = the
+ *   mask value, rgb [n,3] = float32(u8 / 255.0 in fp64), rays_o, rays_d [n,3], near, far [n] = near_tab[frame], far_tab[frame] ([F] fp32).
+ *   status [1] int32 is always written: bit 0 = rows were asked from an empty mask list, bit 1 = from an empty edge list; those rows get
+ *   index -1 and zeros.  The list sizes are read on the device; the lists may be NULL when no row asks for them. */
+int ia_make_rays(int64_t n, const int64_t* pixels, int H, int W, const double* cam_host, float* rays_o, float* rays_d, ia_stream_t stream);
+int ia_window_minmax(int64_t outer, int64_t len, int64_t inner, int k, const float* in, float* out_min, float* out_max, ia_stream_t stream);
+int64_t ia_flag_lists_scratch_bytes(int64_t F, int64_t N);
+int ia_flag_lists_count(int64_t F, int64_t N, const float* mask, const float* mask_i, const float* mask_o, void* scratch, int32_t* totals,
+                        ia_stream_t stream);
+int ia_flag_lists_fill(int64_t F, int64_t N, const float* mask, const float* mask_i, const float* mask_o, const void* scratch,
+                       const int32_t* totals, int32_t* mask_start, int32_t* edge_start, int32_t* counts, int32_t* mask_loc, int32_t* edge_loc,
+                       ia_stream_t stream);
+int ia_sample_batch(int64_t n, int64_t num_mask, int64_t num_edge, int64_t frame, int64_t F, int H, int W, const int64_t* words,
+                    const float* masks, const uint8_t* images, const int32_t* mask_start, const int32_t* edge_start, const int32_t* mask_loc,
+                    const int32_t* edge_loc, const double* cam_host, const float* near_tab, const float* far_tab, int64_t* indices,
+                    float* alpha, float* rgb, float* rays_o, float* rays_d, float* near, float* far, int32_t* status, ia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

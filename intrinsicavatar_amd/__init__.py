@@ -9,6 +9,8 @@ render_step hot path, exposed through the operator surface the reference imports
                                          kernels behind models/pbr/utils.py sample_volume_interaction
     intrinsicavatar_amd.pytorch3d_ops <- `lib.pytorch3d.ops` (knn_points, knn_gather)
     intrinsicavatar_amd.volrend       <- `models/volrend.py` (rendering, rendering_with_normals_sdf, rendering_with_normals_mats_sdf)
+    intrinsicavatar_amd.data          <- `datasets/peoplesnapshot.py` + `utils/sampler.py` (make_rays, EdgeSampler / UniformSampler, the
+                                         training datum from frames resident on the device)
 
 All compute runs in hand-written HIP kernels behind the C ABI of include/ia_amd.h
 (libia_amd.so); PyTorch is used for device memory, streams and torch.distributed only.

@@ -36,6 +36,7 @@ SOURCES = {
     "mcubes.hip": ["-ffp-contract=off"],
     "metrics.hip": ["-ffp-contract=off"],
     "skinning.hip": ["-ffp-contract=off"],
+    "data.hip": ["-ffp-contract=off"],
 }
 
 

@@ -1,0 +1,296 @@
+"""Training batches on the device: camera rays, the pixel samplers and the dataset datum (datasets/peoplesnapshot.py:19-33 and
+:49-175, utils/sampler.py:9-67) on frames that stay resident in HBM.
+
+    make_rays(K, c2w, H, W, device)          make_rays: (rays_o [H,W,3], rays_d [H,W,3]) float32, fp64 arithmetic
+    EdgeSampler / UniformSampler             the reference's constructor arguments, asserts and int() splits; EdgeSampler.edge_band
+    TrainingFrames(images, masks, K, c2w, smpl_params, sampler, near, far)
+        .batch(idx, generator, words)        PeopleSnapshotDataset.__getitem__ (train) as the DataLoader collates it at batch_size 1
+        .full_frame(idx)                     the evaluation form: every pixel in order
+        .check(batch)                        one read-back of the status word -> the reference's ValueError
+    TrainingFrames.from_peoplesnapshot(root, split, start, end, skip, ...)
+
+A step costs torch.randint plus one kernel (csrc/data.hip: ia_sample_batch) and no host synchronisation; the samplers' index lists
+(np.where(mask), np.where(mask_o - mask_i)) are built once per dataset in the constructor, whose one read-back sizes them.
+
+The edge band follows the reference AS WRITTEN: EdgeSampler.sample flattens the mask before cv2.erode / cv2.dilate (utils/sampler.py:27-31),
+so the morphology runs over an N x 1 image -- one 1-D window of kernel_size taps over the flat row-major pixel index, which wraps
+across image rows.  That is the default.  EdgeSampler(..., two_dimensional=True) runs the window over rows, then columns of [H, W]
+instead, which is what the constructor's square kernel suggests.  Conventions and what is unverified: DESIGN.md "Training batches".
+
+The draws are np.random.randint(0, n) replayed as word % n over non-negative int64 words (torch.randint(0, 2**63 - 1) on the device, or
+recorded words).  BalancedSampler and PatchSampler draw with np.random.choice(replace=False), a permutation that cannot be replayed
+from recorded words without restating numpy's generator: their names raise NotImplementedError.
+"""
+import ctypes as C
+import glob
+import os
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from . import _lib as L
+
+MAX_KERNEL_SIZE = 64      # csrc/data_math.h: IA_WINDOW_MAX_K
+
+
+def _need_gpu(device) -> torch.device:
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.IaError("intrinsicavatar_amd operators need GPU tensors (no CPU fallback)")
+    return device
+
+
+def camera_words(K, c2w):
+    """the 21 doubles the kernels take (HOST): inv(K) [9], c2w[:3,:3] [9], c2w[:3,3] [3]; the cameras are taken as float64."""
+    K, c2w = np.asarray(K, np.float64), np.asarray(c2w, np.float64)
+    if K.shape != (3, 3) or c2w.shape[-1] != 4 or c2w.shape[0] < 3:
+        raise ValueError(f"need K [3,3] and c2w [4,4] (or [3,4]), got {K.shape} and {c2w.shape}")
+    vals = np.concatenate([np.linalg.inv(K).reshape(-1), c2w[:3, :3].reshape(-1), c2w[:3, 3].reshape(-1)])
+    return (C.c_double * 21)(*[float(v) for v in vals])
+
+
+def make_rays(K, c2w, H: int, W: int, device) -> Tuple[Tensor, Tensor]:
+    """make_rays (datasets/peoplesnapshot.py:25-33) on the device: (rays_o, rays_d), both [H,W,3] float32."""
+    device = _need_gpu(device)
+    H, W = int(H), int(W)
+    rays_o = torch.empty((H, W, 3), dtype=torch.float32, device=device)
+    rays_d = torch.empty((H, W, 3), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        L.check(L.lib().ia_make_rays(L.i64(H * W), L.ptr(None), L.i32(H), L.i32(W), camera_words(K, c2w), L.ptr(rays_o), L.ptr(rays_d),
+                                     L.stream()), "ia_make_rays")
+    return rays_o, rays_d
+
+
+def window_minmax(x: Tensor, k: int, dim: int = -1) -> Tuple[Tensor, Tensor]:
+    """minimum and maximum of float32 `x` over the k taps at offsets -(k/2) ... k - 1 - k/2 along `dim`, taps outside ignored: the
+    rectangular cv2.erode / cv2.dilate along one axis.  -> (min, max), shaped like x."""
+    if not x.is_cuda:
+        raise L.IaError("intrinsicavatar_amd operators need GPU tensors (no CPU fallback)")
+    if x.dtype != torch.float32:
+        raise TypeError("window_minmax needs float32")
+    x = x.contiguous()
+    dim = dim % x.dim()
+    outer = int(np.prod(x.shape[:dim], dtype=np.int64))
+    inner = int(np.prod(x.shape[dim + 1:], dtype=np.int64))
+    lo, hi = torch.empty_like(x), torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        L.check(L.lib().ia_window_minmax(L.i64(outer), L.i64(x.shape[dim]), L.i64(inner), L.i32(int(k)), L.ptr(x), L.ptr(lo), L.ptr(hi),
+                                         L.stream()), "ia_window_minmax")
+    return lo, hi
+
+
+class UniformSampler:
+    """utils/sampler.py:52-67: num_sample pixels drawn uniformly over the frame."""
+
+    def __init__(self, num_sample):
+        self.num_sample = num_sample
+        self.num_mask = 0
+        self.num_edge = 0
+        self.num_rand = num_sample
+
+
+class EdgeSampler:
+    """utils/sampler.py:9-49: int(num_sample * ratio_mask) pixels from the mask, int(num_sample * ratio_edge) from the edge band
+    dilate(mask) - erode(mask), the rest uniform over the frame.
+
+    The edge band follows the reference as written: `sample` flattens the mask before the morphology, so the kernel_size window runs
+    over the FLAT row-major pixel index (an N x 1 image) and wraps across image rows.  two_dimensional=True runs it over the rows, then
+    the columns of [H, W] instead -- the square kernel the constructor builds."""
+
+    def __init__(self, num_sample, ratio_mask=0.6, ratio_edge=0.3, kernel_size=32, two_dimensional=False):
+        assert ratio_mask >= 0.0
+        assert ratio_edge >= 0.0
+        assert ratio_edge + ratio_mask <= 1.0
+        if not 1 <= int(kernel_size) <= MAX_KERNEL_SIZE:
+            raise ValueError(f"kernel_size must be in [1, {MAX_KERNEL_SIZE}], got {kernel_size}")
+        self.kernel_size = int(kernel_size)
+        self.two_dimensional = bool(two_dimensional)
+        self.num_sample = num_sample
+        self.num_mask = int(num_sample * ratio_mask)
+        self.num_edge = int(num_sample * ratio_edge)
+        self.num_rand = num_sample - self.num_mask - self.num_edge
+
+    def edge_band(self, mask: Tensor) -> Tuple[Tensor, Tensor]:
+        """mask [H,W] or [F,H,W] float32 on the GPU -> (mask_i, mask_o) = (erode, dilate) of every frame, shaped like mask."""
+        if mask.dim() not in (2, 3):
+            raise ValueError(f"edge_band needs [H,W] or [F,H,W], got {tuple(mask.shape)}")
+        if not self.two_dimensional:
+            flat = mask.reshape(-1, mask.shape[-2] * mask.shape[-1]) if mask.dim() == 3 else mask.reshape(-1)
+            lo, hi = window_minmax(flat, self.kernel_size, -1)
+            return lo.view(mask.shape), hi.view(mask.shape)
+        row_lo, row_hi = window_minmax(mask, self.kernel_size, -1)
+        return window_minmax(row_lo, self.kernel_size, -2)[0], window_minmax(row_hi, self.kernel_size, -2)[1]
+
+
+def _unreplayable(name):
+    class _Sampler:
+        def __init__(self, *a, **kw):
+            raise NotImplementedError(f"{name} draws with np.random.choice(replace=False): a permutation that cannot be replayed from "
+                                      "recorded words without restating numpy's generator")
+    _Sampler.__name__ = _Sampler.__qualname__ = name
+    return _Sampler
+
+
+BalancedSampler = _unreplayable("BalancedSampler")
+PatchSampler = _unreplayable("PatchSampler")
+
+# the `_target_` names of configs/sampler/*.yaml
+SAMPLERS = {"utils.sampler.EdgeSampler": EdgeSampler, "utils.sampler.UniformSampler": UniformSampler,
+            "utils.sampler.BalancedSampler": BalancedSampler, "utils.sampler.PatchSampler": PatchSampler}
+
+
+def sampler_from_config(config: dict):
+    """hydra.utils.instantiate for a configs/sampler/*.yaml mapping: {"_target_": "utils.sampler.EdgeSampler", "num_sample": 4096, ...}."""
+    kw = dict(config)
+    return SAMPLERS[kw.pop("_target_")](**kw)
+
+
+def _host(a) -> np.ndarray:
+    return a.detach().cpu().numpy() if isinstance(a, Tensor) else np.asarray(a)
+
+
+class TrainingFrames:
+    """A subject's frames on the device.  images uint8 [F,H,W,3] and masks [F,H,W] are GPU tensors; K [3,3], c2w [4,4] and smpl_params
+    (betas [10] or [1,10], body_pose [F,69], global_orient [F,3], transl [F,3]) are host arrays or tensors.  near / far: the config's
+    values, or (both None) |transl[idx]| -+ 1 as the reference forms them."""
+
+    def __init__(self, images: Tensor, masks: Tensor, K, c2w, smpl_params: Dict, sampler=None, near=None, far=None):
+        if not (images.is_cuda and masks.is_cuda):
+            raise L.IaError("intrinsicavatar_amd operators need GPU tensors (no CPU fallback)")
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
+            raise TypeError(f"images must be uint8 [F,H,W,3], got {images.dtype} {tuple(images.shape)}")
+        if masks.shape != images.shape[:3]:
+            raise ValueError(f"masks {tuple(masks.shape)} do not match images {tuple(images.shape)}")
+        self.device = images.device
+        self.F, self.H, self.W = (int(s) for s in images.shape[:3])
+        self.images = images.contiguous()
+        self.masks = masks.to(torch.float32).contiguous()                    # msk.astype(np.float32)
+        self.sampler = sampler
+        self.cam = camera_words(K, c2w)
+        p = {k: _host(smpl_params[k]).astype(np.float32) for k in ("betas", "body_pose", "global_orient", "transl")}
+        for k in ("body_pose", "global_orient", "transl"):
+            if p[k].shape[0] != self.F:
+                raise ValueError(f"smpl_params[{k!r}] has {p[k].shape[0]} rows for {self.F} frames")
+        self.betas = torch.from_numpy(p["betas"].reshape(1, 10)).to(self.device)
+        self.body_pose, self.global_orient, self.transl = (torch.from_numpy(np.ascontiguousarray(p[k])).to(self.device)
+                                                           for k in ("body_pose", "global_orient", "transl"))
+        if near is not None and far is not None:
+            near_tab = np.ones(self.F, np.float32) * near                   # np.ones_like(rays_d[..., 0]) * self.near
+            far_tab = np.ones(self.F, np.float32) * far
+        else:
+            dist = np.array([np.sqrt(np.square(p["transl"][i]).sum(-1)) for i in range(self.F)], np.float32)
+            near_tab, far_tab = dist - 1, dist + 1
+        self.near = torch.from_numpy(near_tab.astype(np.float32)).to(self.device)
+        self.far = torch.from_numpy(far_tab.astype(np.float32)).to(self.device)
+        self.index = torch.arange(self.F, dtype=torch.int64, device=self.device)
+        self.t_idx = torch.tensor([i / self.F for i in range(self.F)], dtype=torch.float64).to(self.device)
+        self.mask_start = self.edge_start = self.mask_loc = self.edge_loc = self.counts = None
+        if sampler is not None and sampler.num_mask + sampler.num_edge > 0:
+            self._build_lists()
+
+    def _build_lists(self):
+        F, N = self.F, self.H * self.W
+        mask_i, mask_o = self.sampler.edge_band(self.masks)
+        lib, dev = L.lib(), self.device
+        with torch.cuda.device(dev):
+            st = L.stream()
+            scratch = torch.empty(int(lib.ia_flag_lists_scratch_bytes(L.i64(F), L.i64(N))) + 64, dtype=torch.uint8, device=dev)
+            totals = torch.empty(2, dtype=torch.int32, device=dev)
+            args = (L.i64(F), L.i64(N), L.ptr(self.masks), L.ptr(mask_i), L.ptr(mask_o), L.ptr(scratch))
+            L.check(lib.ia_flag_lists_count(*args, L.ptr(totals), st), "ia_flag_lists_count")
+            n_mask, n_edge = (int(v) for v in totals.tolist())              # the one read-back: sizes of the two lists
+            self.mask_start = torch.empty(F + 1, dtype=torch.int32, device=dev)
+            self.edge_start = torch.empty(F + 1, dtype=torch.int32, device=dev)
+            self.counts = torch.empty((F, 2), dtype=torch.int32, device=dev)
+            self.mask_loc = torch.empty(max(n_mask, 1), dtype=torch.int32, device=dev)[:n_mask]
+            self.edge_loc = torch.empty(max(n_edge, 1), dtype=torch.int32, device=dev)[:n_edge]
+            L.check(lib.ia_flag_lists_fill(*args, L.ptr(totals), L.ptr(self.mask_start), L.ptr(self.edge_start), L.ptr(self.counts),
+                                           L.ptr(self.mask_loc), L.ptr(self.edge_loc), st), "ia_flag_lists_fill")
+
+    def __len__(self):
+        return self.F
+
+    def _rows(self, idx: int, n: int, num_mask: int, num_edge: int, words: Optional[Tensor]) -> Dict[str, Tensor]:
+        idx = int(idx)
+        if not 0 <= idx < self.F:
+            raise IndexError(f"frame {idx} outside [0, {self.F})")
+        dev = self.device
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)      # noqa: E731
+        out = {"rgb": f32(1, n, 3), "rays_o": f32(1, n, 3), "rays_d": f32(1, n, 3), "alpha": f32(1, n), "near": f32(1, n), "far": f32(1, n),
+               "pixel_indices": torch.empty((1, n), dtype=torch.int64, device=dev), "status": torch.empty(1, dtype=torch.int32, device=dev)}
+        with torch.cuda.device(dev):
+            L.check(L.lib().ia_sample_batch(
+                L.i64(n), L.i64(num_mask), L.i64(num_edge), L.i64(idx), L.i64(self.F), L.i32(self.H), L.i32(self.W), L.ptr(words),
+                L.ptr(self.masks), L.ptr(self.images), L.ptr(self.mask_start), L.ptr(self.edge_start), L.ptr(self.mask_loc),
+                L.ptr(self.edge_loc), self.cam, L.ptr(self.near), L.ptr(self.far), L.ptr(out["pixel_indices"]), L.ptr(out["alpha"]),
+                L.ptr(out["rgb"]), L.ptr(out["rays_o"]), L.ptr(out["rays_d"]), L.ptr(out["near"]), L.ptr(out["far"]), L.ptr(out["status"]),
+                L.stream()), "ia_sample_batch")
+        s = slice(idx, idx + 1)
+        out.update(betas=self.betas, global_orient=self.global_orient[s], body_pose=self.body_pose[s], transl=self.transl[s],
+                   index=self.index[s], t_idx=self.t_idx[s])
+        return out
+
+    def batch(self, idx: int, generator: Optional[torch.Generator] = None, words: Optional[Tensor] = None) -> Dict[str, Tensor]:
+        """the training datum of frame idx, every entry with the leading dimension of a batch_size-1 DataLoader: rgb, rays_o, rays_d
+        [1,n,3], alpha, near, far [1,n], betas [1,10], global_orient [1,3], body_pose [1,69], transl [1,3], index [1] int64, t_idx [1]
+        float64 = idx / F, + pixel_indices [1,n] int64 and status [1] int32 (check()).  words [n] int64 >= 0 on the device replay a
+        recorded run; otherwise they are drawn with `generator` (a generator of this device).  No host synchronisation."""
+        if self.sampler is None:
+            raise ValueError("TrainingFrames was built without a sampler: only full_frame() is available")
+        n = int(self.sampler.num_sample)
+        if words is None:
+            words = torch.randint(0, 2 ** 63 - 1, (n,), dtype=torch.int64, device=self.device, generator=generator)
+        elif not words.is_cuda:
+            raise L.IaError("intrinsicavatar_amd operators need GPU tensors (no CPU fallback)")
+        elif words.dtype != torch.int64 or tuple(words.shape) != (n,):
+            raise TypeError(f"words must be int64 [{n}], got {words.dtype} {tuple(words.shape)}")
+        return self._rows(idx, n, int(self.sampler.num_mask), int(self.sampler.num_edge), words.contiguous())
+
+    def full_frame(self, idx: int) -> Dict[str, Tensor]:
+        """the evaluation datum of frame idx: all H * W pixels in order, no sampler (status is 0)."""
+        return self._rows(idx, self.H * self.W, 0, 0, None)
+
+    @staticmethod
+    def check(batch: Dict[str, Tensor]) -> None:
+        """reads the batch's status word (one copy to the host); the reference's np.random.randint(0, 0) raises ValueError."""
+        status = int(batch["status"].item())
+        if status:
+            which = " and ".join(name for bit, name in ((1, "mask"), (2, "edge band")) if status & bit)
+            raise ValueError(f"low >= high: the frame's {which} is empty")
+
+    @classmethod
+    def from_peoplesnapshot(cls, root: str, split: str, start: int, end: int, skip: int = 1, sampler=None, near=None, far=None,
+                            refine: bool = False, downscale=1, device="cuda") -> "TrainingFrames":
+        """PeopleSnapshotDataset.__init__ (datasets/peoplesnapshot.py:50-109): cameras.npz, images/*.png (through PIL), masks/*.npy and
+        the pose file the reference picks, read once on the host and moved to `device`."""
+        if downscale != 1:
+            raise NotImplementedError("downscale != 1: every shipped PeopleSnapshot config uses 1, and cv2.resize is not restated here")
+        device = _need_gpu(device)
+        from PIL import Image
+        camera = np.load(os.path.join(root, "cameras.npz"))
+        K = camera["intrinsic"]
+        c2w = np.linalg.inv(camera["extrinsic"])
+        H, W = int(camera["height"]), int(camera["width"])
+        sel = slice(start, end + 1, skip)
+        img_lists = sorted(glob.glob(f"{root}/images/*.png"))[sel]
+        msk_lists = sorted(glob.glob(f"{root}/masks/*.npy"))[sel]
+        if refine:
+            cached_path = os.path.join(root, "poses/anim_nerf_test.npz")
+        elif os.path.exists(os.path.join(root, f"poses/anim_nerf_{split}.npz")):
+            cached_path = os.path.join(root, f"poses/anim_nerf_{split}.npz")
+        elif os.path.exists(os.path.join(root, f"poses/{split}.npz")):
+            cached_path = os.path.join(root, f"poses/{split}.npz")
+        else:
+            cached_path = None
+        cached = bool(cached_path and os.path.exists(cached_path))
+        p = dict(np.load(cached_path if cached else os.path.join(root, "poses.npz")))
+        if "thetas" in p:
+            p["body_pose"], p["global_orient"] = p["thetas"][..., 3:], p["thetas"][..., :3]
+        smpl = {k: p[k] if (cached or k == "betas") else p[k][sel] for k in ("betas", "body_pose", "global_orient", "transl")}
+        images = np.stack([np.asarray(Image.open(f).convert("RGB"), np.uint8) for f in img_lists])
+        masks = np.stack([np.load(f).astype(np.float32) for f in msk_lists])
+        if images.shape[1:3] != (H, W):
+            raise ValueError(f"images are {images.shape[1:3]}, cameras.npz says {(H, W)}")
+        return cls(torch.from_numpy(images).to(device), torch.from_numpy(masks).to(device), K, c2w, smpl, sampler, near, far)
