@@ -121,8 +121,9 @@ int ia_accumulate_along_rays_bwd(int64_t n_samples, int dim, const int64_t* ray_
 
 /* ------------------------------------------------------------------------- */
 /* lib.nerfacc pack / unpack  (lib/nerfacc/pack.py:12-190, cuda/csrc/pack.cu:7-164) */
+int64_t ia_pack_info_tmp_bytes(int64_t n_rays);      /* tmp of ia_pack_info and of ia_resample_packed_info (4-byte aligned) */
 int ia_pack_info(int64_t n_samples, const int64_t* ray_indices, int64_t n_rays,
-                 int32_t* packed_info /*[n,2]*/, void* tmp /* ia_scan_tmp_bytes(n_rays)+4*n_rays+8 bytes */,
+                 int32_t* packed_info /*[n,2]*/, void* tmp /* ia_pack_info_tmp_bytes(n_rays) bytes */,
                  ia_stream_t stream);
 int ia_unpack_info(int64_t n_rays, const int32_t* packed_info, int64_t* ray_indices, ia_stream_t stream);
 int ia_unpack_info_to_mask(int64_t n_rays, const int32_t* packed_info, int n_samples,
@@ -136,7 +137,7 @@ int ia_unpack_data(int64_t n_rays, const int32_t* packed_info, int data_dim, con
  *   cnt = (steps>0 ? n : 0) + (add_steps ? steps : 0); total -> 1 device int32.  */
 int ia_resample_packed_info(int64_t n_rays, const int32_t* packed_info, int n, int add_steps,
                             int32_t* resample_packed_info, int32_t* total,
-                            void* tmp /* ia_scan_tmp_bytes(n_rays)+4*n_rays bytes */, ia_stream_t stream);
+                            void* tmp /* ia_pack_info_tmp_bytes(n_rays) bytes */, ia_stream_t stream);
 /* K1..K4 share one design (csrc/resample_math.h): the launch's sample positions u_j are ONE table, phase A leaves each ray's CDF as a
  * table (one lane per ray: the only serial recurrences), phase B inverts it per OUTPUT element, 64 consecutive elements per store.
  * n_in = number of input intervals (K2: edges), n_out = resample total of ia_resample_packed_info, tmp = ia_resample_tmp_bytes(n_rays,
@@ -300,8 +301,9 @@ int ia_deform_rows_pack(int64_t N, int I, const float* x_rows, const int32_t* cn
  * (out: first_pos [N] = exclusive count of points that have candidates inside the point's tile of 1024, first_tile_off [ceil(N / 1024)] = the
  * tiles' offsets; n_first [1], DEVICE: the number of such points), its other candidates from n_first on, point-major -- the two sub-lists are
  * each spatially coherent in canonical space, which the hash gather that follows needs (a second candidate lies on another body part).
- * scan_tmp: ia_scan_tmp_bytes(N / 1024 + 1) + 4 (N / 1024 + 1) + 512 bytes.  ia_deform_select_min_split = ia_deform_select_min[_scatter] over
+ * scan_tmp: ia_deform_rows_pack_split_tmp_bytes(N) bytes, 8-byte aligned.  ia_deform_select_min_split = ia_deform_select_min[_scatter] over
  * that list (order may be NULL). */
+int64_t ia_deform_rows_pack_split_tmp_bytes(int64_t N);
 int ia_deform_rows_pack_split(int64_t N, int I, const float* x_rows, const int32_t* cnt, const uint32_t* meta, const int32_t* start,
                               const int32_t* ovf_head, const void* ovf_scratch, int32_t* first_pos, int32_t* first_tile_off, int32_t* n_first,
                               float* cand_x, const float* norm_center, const float* norm_scale, void* scan_tmp, ia_stream_t stream);

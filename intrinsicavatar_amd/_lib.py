@@ -27,8 +27,9 @@ class _Timed:
     """optional per-entry-point HIP-event timing (bench.py): events are recorded on the stream the
     kernels are launched on (torch's current stream), nothing synchronises until report()."""
 
-    def __init__(self, cdll):
+    def __init__(self, cdll, untimed=()):
         self._cdll = cdll
+        self._untimed = frozenset(untimed)     # host-only entry points (header_host_only): nothing to put events around
         self.enabled = False
         self.events = {}
 
@@ -41,7 +42,7 @@ class _Timed:
 
     def _resolve(self, name):
         fn = getattr(self._cdll, name)
-        if not name.startswith("ia_") or name in ("ia_last_error", "ia_scan_tmp_bytes", "ia_version", "ia_hashgrid_n_entries", "ia_traverse_scratch_bytes", "ia_occgrid_tmp_bytes", "ia_hashgrid_bwd_scratch_bytes", "ia_traverse_fused_scratch_bytes", "ia_hashgrid_fwd_scratch_bytes", "ia_eikonal_partials", "ia_spec_rows_slots", "ia_spec_rows_overflow_bytes", "ia_spec_rows_overflow_capacity", "ia_resample_tmp_bytes", "ia_sg_image_bwd_tmp_bytes", "ia_envlight_pdf_tables_tmp_bytes", "ia_phys_loss_tmp_bytes", "ia_hashgrid_fwd_levels_jac_offset", "ia_morton_order_tmp_bytes", "ia_deform_filter_tiles_tmp_bytes", "ia_deform_filter_compact_tmp_bytes", "ia_mc_scratch_bytes", "ia_metric_tmp_bytes", "ia_metric_ssim_tmp_bytes", "ia_flag_lists_scratch_bytes"):
+        if not name.startswith("ia_") or name in self._untimed:
             return fn
 
         def call(*args):
@@ -78,16 +79,13 @@ _CTYPE = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t
           "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double, "ia_stream_t": C.c_void_p, "void": None}
 
 
-def header_prototypes(path: str = _HEADER):
-    """{name: (restype, [argtypes])} of every `ia_*` prototype in include/ia_amd.h -- the header is the single source of the
-    ABI: the loader declares argtypes / restype for EVERY entry point from it, so a call with a missing, extra or mistyped
-    argument raises in Python instead of reading garbage off the stack.  Pointers (device or host) are void*."""
+def _header_entries(path: str):
+    """(name, restype, [argtypes], takes_stream) of every `ia_*` prototype in the header"""
     import re
     txt = open(path).read()
     txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
     txt = re.sub(r"//[^\n]*", " ", txt)
     txt = re.sub(r"^\s*#[^\n]*", " ", txt, flags=re.M)                # preprocessor lines
-    protos = {}
     for ret, name, args in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(ia_\w+)\s*\(([^()]*)\)\s*;", txt):
         def ctype(decl, is_ret=False):
             decl = decl.replace("const", " ").strip()
@@ -103,8 +101,20 @@ def header_prototypes(path: str = _HEADER):
         arglist = [a_.strip() for a_ in args.split(",") if a_.strip()]
         if arglist == ["void"]:
             arglist = []
-        protos[name] = (ctype(ret, True), [ctype(a_) for a_ in arglist])
-    return protos
+        yield name, ctype(ret, True), [ctype(a_) for a_ in arglist], any(a_.split()[0] == "ia_stream_t" for a_ in arglist)
+
+
+def header_prototypes(path: str = _HEADER):
+    """{name: (restype, [argtypes])} of every `ia_*` prototype in include/ia_amd.h -- the header is the single source of the
+    ABI: the loader declares argtypes / restype for EVERY entry point from it, so a call with a missing, extra or mistyped
+    argument raises in Python instead of reading garbage off the stack.  Pointers (device or host) are void*."""
+    return {name: (restype, argtypes) for name, restype, argtypes, _ in _header_entries(path)}
+
+
+def header_host_only(path: str = _HEADER):
+    """names of the entry points that enqueue nothing -- size queries, constants, diagnostics: an entry point launches work if
+    and only if its prototype takes an ia_stream_t.  _Timed leaves these unwrapped."""
+    return frozenset(name for name, _, _, takes_stream in _header_entries(path) if not takes_stream)
 
 
 def lib():
@@ -117,10 +127,13 @@ def lib():
         if not os.path.exists(_HEADER):
             raise IaError(f"{_HEADER} not found: the C-ABI header declares the argument types of libia_amd.so")
         cdll = C.CDLL(_SO)
-        for name, (restype, argtypes) in header_prototypes().items():
+        host_only = []
+        for name, restype, argtypes, takes_stream in _header_entries(_HEADER):
             fn = getattr(cdll, name)              # AttributeError: the header declares a symbol the library does not export
             fn.restype, fn.argtypes = restype, argtypes
-        _lib = _Timed(cdll)
+            if not takes_stream:
+                host_only.append(name)
+        _lib = _Timed(cdll, host_only)
     return _lib
 
 
@@ -182,9 +195,17 @@ def scratch_clear():
     _SCRATCH.clear()
 
 
-def scan_tmp(n: int, device, extra_bytes: int = 0):
-    nbytes = int(lib().ia_scan_tmp_bytes(C.c_int64(max(int(n), 1)))) + int(extra_bytes) + 64
-    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+def work_area(nbytes: int, device, name: str = None):
+    """the `tmp` / `scratch` of one entry-point call: `nbytes` (what the entry point's ia_*_bytes query returned -- the library measures
+    a work area with the code that carves it, nothing is added here) as a uint8 tensor; a fresh one, or with `name` the grow-only
+    buffer of that name (scratch() above: which call sites take it was measured)."""
+    if name is not None:
+        return scratch(name, nbytes, device)
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
+def scan_tmp(n: int, device):
+    return work_area(int(lib().ia_scan_tmp_bytes(C.c_int64(max(int(n), 1)))) + 64, device)      # (+ 64: slack every scan caller has always had)
 
 
 _ZEROS_FILL = os.environ.get("IA_ZEROS", "fill") == "fill"

@@ -198,11 +198,16 @@ __global__ __launch_bounds__(DT) void sample_kernel(int64_t n, int64_t num_mask,
     }
 }
 
-Lists carve(void* scratch, int64_t blocks)
+// per-block counts of the two lists, their exclusive scans, the scan work area; scratch 8-byte aligned
+size_t lists_layout(void* scratch, int64_t blocks, Lists* L)
 {
-    int32_t* s = (int32_t*)scratch;
-    const int64_t b = (blocks + 1) / 2 * 2;              // keeps the scan's work area 8-byte aligned
-    return Lists{s, s + b, s + 2 * b, s + 3 * b, (void*)(s + 4 * b)};
+    ia::Carver c(scratch);
+    L->mcnt = c.take<int32_t>((size_t)blocks, 8);
+    L->ecnt = c.take<int32_t>((size_t)blocks, 8);
+    L->mstart = c.take<int32_t>((size_t)blocks, 8);
+    L->estart = c.take<int32_t>((size_t)blocks, 8);
+    L->scan_tmp = c.take<char>((size_t)ia_scan_tmp_bytes(blocks), 8);
+    return c.need(8);
 }
 
 bool lists_dims(int64_t F, int64_t N, int64_t* bpf, int64_t* blocks)
@@ -258,7 +263,8 @@ IA_EXPORT int64_t ia_flag_lists_scratch_bytes(int64_t F, int64_t N)
 {
     int64_t bpf, blocks;
     if (!lists_dims(F, N, &bpf, &blocks)) return 0;
-    return 4 * ((blocks + 1) / 2 * 2) * 4 + ia_scan_tmp_bytes(blocks);
+    Lists L;
+    return (int64_t)lists_layout(nullptr, blocks, &L);
 }
 
 IA_EXPORT int ia_flag_lists_count(int64_t F, int64_t N, const float* mask, const float* mask_i, const float* mask_o, void* scratch,
@@ -267,7 +273,8 @@ IA_EXPORT int ia_flag_lists_count(int64_t F, int64_t N, const float* mask, const
     int64_t bpf, blocks;
     IA_REQUIRE(lists_dims(F, N, &bpf, &blocks), "need F >= 1 frames of N >= 1 pixels with F * N < 2^31");
     IA_REQUIRE(mask && mask_i && mask_o && scratch && totals, "null pointer");
-    const Lists L = carve(scratch, blocks);
+    Lists L;
+    lists_layout(scratch, blocks, &L);
     lists_count_kernel<<<(unsigned)blocks, DT, 0, (hipStream_t)stream>>>(bpf, N, mask, mask_i, mask_o, L.mcnt, L.ecnt);
     int r = ia::check_launch("ia_flag_lists_count");
     if (r != IA_OK) return r;
@@ -283,7 +290,8 @@ IA_EXPORT int ia_flag_lists_fill(int64_t F, int64_t N, const float* mask, const 
     int64_t bpf, blocks;
     IA_REQUIRE(lists_dims(F, N, &bpf, &blocks), "need F >= 1 frames of N >= 1 pixels with F * N < 2^31");
     IA_REQUIRE(mask && mask_i && mask_o && scratch && totals && mask_start && edge_start && counts, "null pointer");
-    const Lists L = carve((void*)scratch, blocks);
+    Lists L;
+    lists_layout((void*)scratch, blocks, &L);
     lists_fill_kernel<<<(unsigned)blocks, DT, 0, (hipStream_t)stream>>>(F, bpf, N, mask, mask_i, mask_o, L.mstart, L.estart, totals, mask_start,
                                                                        edge_start, counts, mask_loc, edge_loc);
     return ia::check_launch("ia_flag_lists_fill");

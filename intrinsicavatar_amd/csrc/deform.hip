@@ -612,9 +612,47 @@ IA_EXPORT int ia_deform_compact(int64_t P, int I, const float* x, const uint8_t*
     return ia::check_launch("ia_deform_compact");
 }
 
+// ia_deform_filter_compact: one look-back descriptor per tile; tmp 8-byte aligned
+struct FilterCompactTmp {
+    uint64_t* desc;
+    int64_t n_tiles;
+    bool fits;
+};
+
+static size_t filter_compact_layout(void* tmp, size_t bytes, int64_t P, FilterCompactTmp* t)
+{
+    t->n_tiles = ia::cdiv(P > 0 ? P : 1, FCC_ROWS);
+    ia::Carver c(tmp, bytes);
+    t->desc = c.take<uint64_t>((size_t)t->n_tiles, 8);
+    c.skip(16);
+    t->fits = c.fits();
+    return c.need(8);
+}
+
+// ia_deform_filter_tiles -> ia_deform_pack_tiles: tile totals, their exclusive scan, the scan work area; tmp 8-byte aligned
+struct FilterTilesTmp {
+    int32_t *tile_tot, *tile_off;
+    void* scan_tmp;
+    int64_t n_tiles;
+    bool fits;
+};
+
+static size_t filter_tiles_layout(void* tmp, size_t bytes, int64_t P, FilterTilesTmp* t)
+{
+    t->n_tiles = ia::cdiv(P > 0 ? P : 1, FCC_ROWS);
+    ia::Carver c(tmp, bytes);
+    t->tile_tot = c.take<int32_t>((size_t)t->n_tiles, 8);
+    t->tile_off = c.take<int32_t>((size_t)t->n_tiles, 4);
+    t->scan_tmp = c.take<char>((size_t)ia_scan_tmp_bytes(t->n_tiles), 8);
+    c.skip(64);                                          // tail slack, as the callers have always allocated
+    t->fits = c.fits();
+    return c.need(8);
+}
+
 IA_EXPORT size_t ia_deform_filter_compact_tmp_bytes(int64_t P)
 {
-    return (size_t)(ia::cdiv(P > 0 ? P : 1, FCC_ROWS)) * sizeof(uint64_t) + 16;
+    FilterCompactTmp t;
+    return filter_compact_layout(nullptr, SIZE_MAX, P, &t);
 }
 
 IA_EXPORT int ia_deform_filter_compact(int64_t P, int I, const float* x, const uint8_t* valid, int32_t* cnt, int32_t* start,
@@ -629,12 +667,13 @@ IA_EXPORT int ia_deform_filter_compact(int64_t P, int I, const float* x, const u
     }
     IA_REQUIRE(I >= 1 && I <= FC_MAX_I, "ia_deform_filter_compact: at most 16 initialisations per point");
     IA_REQUIRE(P * I < ((int64_t)1 << 31), "ia_deform_filter_compact: P * I must stay below 2^31");
-    const int64_t n_tiles = ia::cdiv(P, FCC_ROWS);
-    const size_t need = ia_deform_filter_compact_tmp_bytes(P);
-    IA_REQUIRE(tmp != nullptr && tmp_bytes >= need, "ia_deform_filter_compact: tmp too small (ia_deform_filter_compact_tmp_bytes)");
+    FilterCompactTmp t;
+    const size_t need = filter_compact_layout(tmp, tmp_bytes, P, &t);
+    IA_REQUIRE(tmp != nullptr && t.fits, "ia_deform_filter_compact: tmp too small (ia_deform_filter_compact_tmp_bytes)");
     IA_REQUIRE((reinterpret_cast<uintptr_t>(tmp) & 7) == 0, "ia_deform_filter_compact: tmp must be 8-byte aligned");
+    const int64_t n_tiles = t.n_tiles;
+    uint64_t* desc = t.desc;
     if (hipMemsetAsync(tmp, 0, need, s) != hipSuccess) return ia::check_launch("ia_deform_filter_compact(memset)");
-    uint64_t* desc = reinterpret_cast<uint64_t*>(tmp);
     const uint32_t magic = (uint32_t)((((uint64_t)1 << 32) + (uint64_t)I - 1) / (uint64_t)I);   // e / I for e < 2^16 (checked for I <= 16)
     const size_t lds = (size_t)FCC_ROWS * I * 3 * sizeof(float) + (size_t)FCC_ROWS * I + 16;
     const unsigned grid = (unsigned)n_tiles;
@@ -656,8 +695,8 @@ IA_EXPORT int ia_deform_filter_compact(int64_t P, int I, const float* x, const u
 // tmp: ia_deform_filter_tiles_tmp_bytes(P) bytes, 8-byte aligned, kept between the two calls.
 IA_EXPORT size_t ia_deform_filter_tiles_tmp_bytes(int64_t P)
 {
-    const int64_t n_tiles = ia::cdiv(P > 0 ? P : 1, FCC_ROWS);
-    return (size_t)n_tiles * 8 + (size_t)ia_scan_tmp_bytes(n_tiles) + 64;
+    FilterTilesTmp t;
+    return filter_tiles_layout(nullptr, SIZE_MAX, P, &t);
 }
 
 IA_EXPORT int ia_deform_filter_tiles(int64_t P, int I, float* x, const uint8_t* valid, int32_t* cnt, int32_t* start, int32_t* src_local,
@@ -671,12 +710,13 @@ IA_EXPORT int ia_deform_filter_tiles(int64_t P, int I, float* x, const uint8_t* 
     }
     IA_REQUIRE(I >= 1 && I <= FC_MAX_I, "ia_deform_filter_tiles: at most 16 initialisations per point");
     IA_REQUIRE(P * I < ((int64_t)1 << 31), "ia_deform_filter_tiles: P * I must stay below 2^31");
-    const int64_t n_tiles = ia::cdiv(P, FCC_ROWS);
-    IA_REQUIRE(tmp != nullptr && tmp_bytes >= ia_deform_filter_tiles_tmp_bytes(P), "ia_deform_filter_tiles: tmp too small");
+    FilterTilesTmp t;
+    filter_tiles_layout(tmp, tmp_bytes, P, &t);
+    IA_REQUIRE(tmp != nullptr && t.fits, "ia_deform_filter_tiles: tmp too small");
     IA_REQUIRE((reinterpret_cast<uintptr_t>(tmp) & 7) == 0, "ia_deform_filter_tiles: tmp must be 8-byte aligned");
-    int32_t* tile_tot = reinterpret_cast<int32_t*>(tmp);
-    int32_t* tile_off = tile_tot + n_tiles;
-    void* scan_tmp = reinterpret_cast<char*>(tmp) + (size_t)n_tiles * 8;
+    const int64_t n_tiles = t.n_tiles;
+    int32_t *tile_tot = t.tile_tot, *tile_off = t.tile_off;
+    void* scan_tmp = t.scan_tmp;
     const uint32_t magic = (uint32_t)((((uint64_t)1 << 32) + (uint64_t)I - 1) / (uint64_t)I);
     const size_t lds = (size_t)FCC_ROWS * I * 3 * sizeof(float) + (size_t)FCC_ROWS * I + 16;
     const unsigned grid = (unsigned)n_tiles;
@@ -697,9 +737,10 @@ IA_EXPORT int ia_deform_pack_tiles(int64_t P, int I, const float* x, const int32
     if (P == 0) return IA_OK;
     IA_REQUIRE(cand_x != x, "ia_deform_pack_tiles: cand_x must not alias x");
     IA_REQUIRE((cand_src == nullptr) == (src_local == nullptr), "ia_deform_pack_tiles: cand_src and src_local come together");
-    const int64_t n_tiles = ia::cdiv(P, FCC_ROWS);
-    const int32_t* tile_tot = reinterpret_cast<const int32_t*>(tmp);
-    const int32_t* tile_off = tile_tot + n_tiles;
+    FilterTilesTmp t;
+    filter_tiles_layout(const_cast<void*>(tmp), SIZE_MAX, P, &t);
+    const int64_t n_tiles = t.n_tiles;
+    const int32_t *tile_tot = t.tile_tot, *tile_off = t.tile_off;
     pack_tiles_kernel<<<(unsigned)n_tiles, FCC_ROWS, 0, (hipStream_t)stream>>>(P, I, x, src_local, tile_off, tile_tot, start, cand_x,
                                                                                 cand_src);
     return ia::check_launch("ia_deform_pack_tiles");

@@ -1080,10 +1080,32 @@ IA_EXPORT int ia_hashgrid_fwd(int64_t n, const float* x, const float* params, in
 }
 
 
+// level-major results of the XCD-partitioned gather: float2 [L][n] | float [L][n][6] (with_jac).  The caller of ia_hashgrid_fwd_levels reads
+// the results THROUGH jac_offset, so the layout is one of offsets (a measuring pass) and does not depend on the pointer's alignment.
+struct HashFwdScratch {
+    float2* feat;
+    float* jac;
+    int64_t jac_offset;
+};
+
+static size_t hash_fwd_layout(void* scratch, int64_t n, int n_levels, int with_jac, HashFwdScratch* o)
+{
+    ia::Carver c(nullptr);
+    c.take<float2>((size_t)(n * n_levels), 1);
+    c.align_to(256);
+    o->jac_offset = (int64_t)c.used();
+    if (with_jac) c.take<float>((size_t)(n * n_levels) * 6, 1);
+    c.skip(256);                                        // tail slack, as before
+    o->feat = reinterpret_cast<float2*>(scratch);
+    o->jac = scratch && with_jac ? reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + o->jac_offset) : nullptr;
+    return c.used();
+}
+
 IA_EXPORT int64_t ia_hashgrid_fwd_scratch_bytes(int64_t n, int n_levels, int with_jac)
 {
     if (n < 0 || n_levels <= 0 || n_levels > MAX_LEVELS) return -1;
-    return n * n_levels * 8 + (with_jac ? n * n_levels * 24 : 0) + 256;
+    HashFwdScratch w;
+    return (int64_t)hash_fwd_layout(nullptr, n, n_levels, with_jac, &w);
 }
 
 // same outputs as ia_hashgrid_fwd; scratch = ia_hashgrid_fwd_scratch_bytes(n, n_levels, dy_dx != NULL) bytes
@@ -1098,8 +1120,10 @@ IA_EXPORT int ia_hashgrid_fwd_xcd(int64_t n, const float* x, const float* params
     IA_REQUIRE(scratch != nullptr, "scratch required");
     HashCfg c;
     make_cfg(c, n_levels, log2_hashmap_size, base_resolution, per_level_scale);
-    float2* tmp = (float2*)scratch;
-    float* tmp_jac = dy_dx ? (float*)((char*)scratch + ((n * n_levels * 8 + 255) / 256) * 256) : nullptr;
+    HashFwdScratch w;
+    hash_fwd_layout(scratch, n, n_levels, dy_dx != nullptr, &w);
+    float2* tmp = w.feat;
+    float* tmp_jac = w.jac;
     // level sets: "big" levels own a full 2^log2_hashmap_size table (one L2 each), the rest are the small dense ones
     const uint32_t cap = 1u << log2_hashmap_size;
     int n_small = 0;
@@ -1212,7 +1236,9 @@ IA_EXPORT int ia_hashgrid_fwd_xcd(int64_t n, const float* x, const float* params
 // level-major results only: float2 [L][n] at scratch, and (with_jac) float [L][n][6] at scratch + ia_hashgrid_fwd_levels_jac_offset
 IA_EXPORT int64_t ia_hashgrid_fwd_levels_jac_offset(int64_t n, int n_levels)
 {
-    return ((n * n_levels * 8 + 255) / 256) * 256;
+    HashFwdScratch w;
+    hash_fwd_layout(nullptr, n, n_levels, 1, &w);
+    return w.jac_offset;
 }
 
 IA_EXPORT int ia_hashgrid_fwd_levels(int64_t n, const float* x, const float* params, int n_levels, int n_features, int log2_hashmap_size,
@@ -1244,9 +1270,17 @@ IA_EXPORT int ia_hashgrid_bwd(int64_t n, const float* x, int n_levels, int n_fea
 
 
 namespace {
+// work area of the binned backward: [n_buckets][nwg] counts (scanned in place) | total | level_max [MAX_LEVELS] | the reduction's plan |
+// scan work area | record values | record indices; any alignment of scratch
 struct BinLayout {
     int nwg; int64_t m, records;
-    int64_t off_counts, off_total, off_tmp, off_val, off_idx, bytes;
+    int32_t *counts, *total;
+    unsigned* level_max;
+    int32_t* plan;
+    void* tmp;
+    float2* rec_val;
+    uint16_t* rec_idx;
+    bool fits;
 };
 bool staged_fill()
 {
@@ -1258,20 +1292,21 @@ bool staged_fill()
     return mode == 1;
 }
 
-BinLayout bin_layout(int64_t n, int n_levels, int n_buckets)
+size_t bin_layout(void* scratch, size_t bytes, int64_t n, int n_levels, int n_buckets, BinLayout* L)
 {
-    BinLayout L;
-    L.nwg = staged_fill() ? ia::cdiv(n, U_PTS) : ia::cdiv(n, BIN_TILE);       // units of the count matrix
-    L.m = (int64_t)n_buckets * L.nwg;
-    L.records = n * n_levels * 8;
-    auto up = [](int64_t v) { return (v + 255) / 256 * 256; };
-    L.off_counts = 0;
-    L.off_total = up(L.m * 4);
-    L.off_tmp = L.off_total + 512 + 4 * (MAX_BUCKETS + 64);      // total (4 B), level_max[32] at +256, plan at +512
-    L.off_val = up(L.off_tmp + ia_scan_tmp_bytes(L.m));
-    L.off_idx = up(L.off_val + L.records * 8);
-    L.bytes = up(L.off_idx + L.records * 2);
-    return L;
+    L->nwg = staged_fill() ? ia::cdiv(n, U_PTS) : ia::cdiv(n, BIN_TILE);       // units of the count matrix
+    L->m = (int64_t)n_buckets * L->nwg;
+    L->records = n * n_levels * 8;
+    ia::Carver c(scratch, bytes);
+    L->counts = c.take<int32_t>((size_t)L->m);
+    L->total = c.take<int32_t>(1);
+    L->level_max = c.take<unsigned>(MAX_LEVELS);
+    L->plan = c.take<int32_t>(MAX_BUCKETS + 64);
+    L->tmp = c.take<char>((size_t)ia_scan_tmp_bytes(L->m));
+    L->rec_val = c.take<float2>((size_t)L->records);
+    L->rec_idx = c.take<uint16_t>((size_t)L->records);
+    L->fits = c.fits();
+    return c.need(1);
 }
 }  // namespace
 
@@ -1284,7 +1319,8 @@ IA_EXPORT int64_t ia_hashgrid_bwd_scratch_bytes(int64_t n, int n_levels, int log
     BinCfg b;
     make_bins(b, c);
     if (b.n_buckets > MAX_BUCKETS) return -1;
-    return bin_layout(n, n_levels, b.n_buckets).bytes;
+    BinLayout L;
+    return (int64_t)bin_layout(nullptr, SIZE_MAX, n, n_levels, b.n_buckets, &L);
 }
 
 IA_EXPORT int ia_hashgrid_bwd_binned(int64_t n, const float* x, int n_levels, int n_features, int log2_hashmap_size,
@@ -1303,16 +1339,15 @@ IA_EXPORT int ia_hashgrid_bwd_binned(int64_t n, const float* x, int n_levels, in
     BinCfg b;
     make_bins(b, c);
     IA_REQUIRE(b.n_buckets <= MAX_BUCKETS, "too many (level, slice) buckets");
-    const BinLayout L = bin_layout(n, n_levels, b.n_buckets);
-    IA_REQUIRE(scratch != nullptr && scratch_bytes >= L.bytes, "scratch smaller than ia_hashgrid_bwd_scratch_bytes(n)");
-    char* base = (char*)scratch;
-    int32_t* counts = (int32_t*)(base + L.off_counts);
-    int32_t* total = (int32_t*)(base + L.off_total);
-    void* tmp = base + L.off_tmp;
-    float2* rec_val = (float2*)(base + L.off_val);
-    uint16_t* rec_idx = (uint16_t*)(base + L.off_idx);
+    BinLayout L;
+    bin_layout(scratch, scratch_bytes > 0 ? (size_t)scratch_bytes : 0, n, n_levels, b.n_buckets, &L);       // (a negative size fits nothing)
+    IA_REQUIRE(scratch != nullptr && L.fits, "scratch smaller than ia_hashgrid_bwd_scratch_bytes(n)");
+    int32_t *counts = L.counts, *total = L.total;
+    void* tmp = L.tmp;
+    float2* rec_val = L.rec_val;
+    uint16_t* rec_idx = L.rec_idx;
     hipStream_t s = (hipStream_t)stream;
-    unsigned* level_max = (unsigned*)(base + L.off_total + 256);
+    unsigned* level_max = L.level_max;
     if (hipMemsetAsync(level_max, 0, MAX_LEVELS * sizeof(unsigned), s) != hipSuccess) return ia::check_launch("ia_hashgrid_bwd_binned(memset)");
     const bool staged = staged_fill();
     const int ugrid = ia::cdiv(L.nwg, U_WAVES);
@@ -1347,7 +1382,7 @@ IA_EXPORT int ia_hashgrid_bwd_binned(int64_t n, const float* x, int n_levels, in
         (void)hipGetLastError();
         attr = true;
     }
-    int32_t* plan = (int32_t*)(base + L.off_total + 512);
+    int32_t* plan = L.plan;
     hash_plan_kernel<<<1, 1024, 0, s>>>(b, L.nwg, counts, total, plan);
     hash_reduce_kernel<<<256, RTHREADS, red_lds, s>>>(c, b, L.nwg, counts, total, rec_idx, rec_val, level_max, plan, grad_params);
     return ia::check_launch("ia_hashgrid_bwd_binned");

@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/ia_amd.h"
+#include "ia_scratch.h"
 
 #define IA_EXPORT extern "C" __attribute__((visibility("default")))
 

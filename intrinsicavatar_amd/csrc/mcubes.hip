@@ -189,10 +189,16 @@ struct Scratch {
     void* scan_tmp;
 };
 
-Scratch carve(void* scratch, int64_t blocks)
+// per-block vertex / triangle counts, their exclusive scans, the scan work area; scratch 8-byte aligned
+size_t mc_layout(void* scratch, int64_t blocks, Scratch* sc)
 {
-    int64_t* s = (int64_t*)scratch;
-    return Scratch{s, s + blocks, s + 2 * blocks, s + 3 * blocks, (void*)(s + 4 * blocks)};
+    ia::Carver c(scratch);
+    sc->vcnt = c.take<int64_t>((size_t)blocks, 8);
+    sc->tcnt = c.take<int64_t>((size_t)blocks, 8);
+    sc->vstart = c.take<int64_t>((size_t)blocks, 8);
+    sc->tstart = c.take<int64_t>((size_t)blocks, 8);
+    sc->scan_tmp = c.take<char>((size_t)ia_scan_tmp_bytes(blocks), 8);
+    return c.need(8);
 }
 
 bool dims_ok(int nx, int ny, int nz, Dims* d)
@@ -209,7 +215,8 @@ bool dims_ok(int nx, int ny, int nz, Dims* d)
 IA_EXPORT int64_t ia_mc_scratch_bytes(int nx, int ny, int nz)
 {
     const int64_t blocks = n_blocks((int64_t)(nx > 0 ? nx : 0) * (ny > 0 ? ny : 0) * (nz > 0 ? nz : 0));
-    return 4 * blocks * 8 + ia_scan_tmp_bytes(blocks);
+    Scratch sc;
+    return (int64_t)mc_layout(nullptr, blocks, &sc);
 }
 
 IA_EXPORT int ia_mc_count(int nx, int ny, int nz, const float* level, float threshold, void* scratch, int64_t* totals,
@@ -220,7 +227,8 @@ IA_EXPORT int ia_mc_count(int nx, int ny, int nz, const float* level, float thre
     IA_REQUIRE(level && scratch && totals, "null pointer");
     const hipStream_t s = (hipStream_t)stream;
     const int64_t blocks = n_blocks(d.n);
-    const Scratch sc = carve(scratch, blocks);
+    Scratch sc;
+    mc_layout(scratch, blocks, &sc);
     mc_count_kernel<<<(unsigned)blocks, MC_THREADS, 0, s>>>(level, d, threshold, sc.vcnt, sc.tcnt);
     int r = ia::check_launch("ia_mc_count");
     if (r != IA_OK) return r;
@@ -237,7 +245,8 @@ IA_EXPORT int ia_mc_emit(int nx, int ny, int nz, const float* level, float thres
     IA_REQUIRE(level && box && scratch && first_vid && v_pos && t_pos_idx, "null pointer");
     const hipStream_t s = (hipStream_t)stream;
     const int64_t blocks = n_blocks(d.n);
-    const Scratch sc = carve((void*)scratch, blocks);
+    Scratch sc;
+    mc_layout((void*)scratch, blocks, &sc);
     mc_emit_kernel<<<(unsigned)blocks, MC_THREADS, 0, s>>>(level, d, threshold, sc.vstart, box[0], box[1], box[2], box[3], box[4], box[5],
                                                           first_vid, v_pos);
     mc_face_kernel<<<(unsigned)blocks, MC_THREADS, 0, s>>>(level, d, threshold, sc.tstart, first_vid, t_pos_idx);

@@ -151,12 +151,34 @@ IA_EXPORT int ia_occgrid_ema(int64_t n_cells, float* occs, const float* occ_new,
     return ia::check_launch("ia_occgrid_ema");
 }
 
+// pooled f32[n] | labels A i32[n] | labels B i32[n] | hist i32[n+2] | part_sum f64[parts] | part_cnt i64[parts] | best; tmp 4-byte aligned
+struct BinarizeTmp {
+    float* pooled;
+    int32_t *labA, *labB, *hist;
+    double* part_sum;
+    int64_t* part_cnt;
+    int32_t* best;
+};
+
+static size_t binarize_layout(void* tmp, int64_t n, BinarizeTmp* t)
+{
+    const size_t cells = (size_t)(n > 0 ? n : 0), parts = (cells + THREADS - 1) / THREADS;
+    ia::Carver c(tmp);
+    t->pooled = c.take<float>(cells, 4);
+    t->labA = c.take<int32_t>(cells, 4);
+    t->labB = c.take<int32_t>(cells, 4);
+    t->hist = c.take<int32_t>(cells + 2, 4);
+    t->part_sum = c.take<double>(parts, 16);
+    t->part_cnt = c.take<int64_t>(parts, 8);
+    t->best = c.take<int32_t>(1, 4);
+    c.skip(64);                                          // tail slack, as the callers have always allocated
+    return c.need(4);
+}
+
 IA_EXPORT int64_t ia_occgrid_tmp_bytes(int rx, int ry, int rz)
 {
-    const int64_t n = (int64_t)rx * ry * rz;
-    const int64_t parts = (n + THREADS - 1) / THREADS;
-    // pooled f32[n] | labels A i32[n] | labels B i32[n] | hist i32[n+1] | part_sum f64[parts] | part_cnt i64[parts] | best
-    return 4 * n * 3 + 4 * (n + 2) + 16 * parts + 64;
+    BinarizeTmp t;
+    return (int64_t)binarize_layout(nullptr, (int64_t)rx * ry * rz, &t);
 }
 
 IA_EXPORT int ia_occgrid_binarize(int rx, int ry, int rz, const float* occs, float thre_max, int keep_largest_component,
@@ -166,13 +188,12 @@ IA_EXPORT int ia_occgrid_binarize(int rx, int ry, int rz, const float* occs, flo
     const int64_t n = (int64_t)rx * ry * rz;
     const int grid = ia::cdiv(n, THREADS);
     hipStream_t s = (hipStream_t)stream;
-    float* pooled = (float*)tmp;
-    int32_t* labA = (int32_t*)(pooled + n);
-    int32_t* labB = labA + n;
-    int32_t* hist = labB + n;
-    double* part_sum = (double*)(((uintptr_t)(hist + n + 2) + 15) & ~(uintptr_t)15);
-    int64_t* part_cnt = (int64_t*)(part_sum + grid);
-    int32_t* best = (int32_t*)(part_cnt + grid);
+    BinarizeTmp t;
+    binarize_layout(tmp, n, &t);
+    float* pooled = t.pooled;
+    int32_t *labA = t.labA, *labB = t.labB, *hist = t.hist, *best = t.best;
+    double* part_sum = t.part_sum;
+    int64_t* part_cnt = t.part_cnt;
     dilate_kernel<<<grid, THREADS, 0, s>>>(rx, ry, rz, occs, pooled, part_sum, part_cnt);
     threshold_kernel<<<grid, THREADS, 0, s>>>(n, grid, pooled, part_sum, part_cnt, thre_max, binaries, thre_out);
     if (keep_largest_component) {

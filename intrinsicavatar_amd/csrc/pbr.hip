@@ -790,15 +790,49 @@ constexpr size_t ENV_FIXED_MAX_TEXELS = (size_t)1 << 21;       // 1024 x 2048
 extern "C" int64_t ia_scan_tmp_bytes(int64_t n);
 extern "C" int ia_exclusive_scan_i32(const int32_t* in, int32_t* out, int32_t* total, int64_t n, void* tmp, ia_stream_t stream);
 
+// work area of the banded image-gradient path: SoA records of the backward kernel (24 B each) | band-sorted AoS records | [32][n_tiles]
+// counts | the same, scanned | total | max |g| | scan work area | the 64-bit fixed-point image (sized for the largest map the fixed-point
+// path takes: 2^21 texels).  scratch 16-byte aligned.
+struct EnvBwdScratch {
+    uint32_t* rec_idx;
+    float2* rec_w;
+    float* rec_g;
+    EnvRec* sorted;
+    int32_t *counts, *offs, *total;
+    uint32_t* gmax;
+    void* scan_tmp;
+    unsigned long long* acc64;
+    bool fits;
+};
+
+static size_t env_bwd_layout(void* scratch, size_t bytes, int64_t F, EnvBwdScratch* o)
+{
+    const size_t n4 = ((size_t)F + 3) & ~(size_t)3;
+    const size_t n_tiles = ((size_t)F + ENV_TILE - 1) / ENV_TILE;
+    ia::Carver c(scratch, bytes);
+    o->rec_idx = c.take<uint32_t>(n4, 16);            // the three record columns lie back to back (n4 is a multiple of 4)
+    o->rec_w = c.take<float2>(n4, 16);
+    o->rec_g = c.take<float>(3 * n4, 16);
+    c.skip(64);
+    o->sorted = c.take<EnvRec>(n4, 16);
+    o->counts = c.take<int32_t>(32 * n_tiles, 16);
+    c.skip(64);
+    o->offs = c.take<int32_t>(32 * n_tiles, 16);
+    c.skip(64);
+    o->total = c.take<int32_t>(4, 16);
+    o->gmax = c.take<uint32_t>(12, 16);
+    o->scan_tmp = c.take<char>((size_t)ia_scan_tmp_bytes((int64_t)(32 * n_tiles)));
+    o->acc64 = c.take<unsigned long long>(ENV_FIXED_MAX_TEXELS * 3);
+    c.skip(256);                                          // tail slack, as the callers have always allocated
+    o->fits = c.fits();
+    return c.need(16);
+}
+
 IA_EXPORT size_t ia_pbr_shade_bwd_scratch_bytes(int64_t F)
 {
     if (F < ENV_ACC_MIN_F) return 0;                 // small batches scatter with atomics directly
-    // SoA records of the backward kernel (24 B each) | band-sorted AoS records (24 B each) | [32][n_tiles] counts | the same, scanned |
-    // total, max |g| | scan scratch | the 64-bit fixed-point image (sized for the largest map the fixed-point path takes: 2^21 texels)
-    const size_t n4 = ((size_t)F + 3) & ~(size_t)3;
-    const size_t n_tiles = ((size_t)F + ENV_TILE - 1) / ENV_TILE;
-    return n4 * 24 + 64 + n4 * 24 + 2 * (32 * n_tiles * 4 + 64) + 64 + (size_t)ia_scan_tmp_bytes((int64_t)(32 * n_tiles)) + 512 +
-           ENV_FIXED_MAX_TEXELS * 3 * 8;
+    EnvBwdScratch w;
+    return env_bwd_layout(nullptr, SIZE_MAX, F, &w);
 }
 
 IA_EXPORT int ia_pbr_shade_bwd(int mode, int64_t F, const float* normal, const float* albedo, const float* roughness,
@@ -820,17 +854,15 @@ IA_EXPORT int ia_pbr_shade_bwd(int mode, int64_t F, const float* normal, const f
     uint32_t* rec_idx = nullptr;
     float2* rec_w = nullptr;
     float* rec_g = nullptr;
+    EnvBwdScratch w{};
     int TH = 0, n_bands = 0;
     if (g_env_base && scratch && F >= ENV_ACC_MIN_F && env_h <= 32767 && env_w <= 65535 && !getenv("IA_ENV_GRAD_ATOMIC")) {
         const int rows = ENV_ACC_LDS / (env_w * 3 * (int)sizeof(float));
         TH = rows - 1;
         n_bands = TH >= 1 ? (env_h + TH - 1) / TH : 0;
-        if (TH >= 1 && n_bands <= 32 && scratch_bytes >= ia_pbr_shade_bwd_scratch_bytes(F) &&
-            (reinterpret_cast<uintptr_t>(scratch) & 15) == 0) {
-            const size_t n4 = ((size_t)F + 3) & ~(size_t)3;
-            rec_idx = reinterpret_cast<uint32_t*>(scratch);
-            rec_w = reinterpret_cast<float2*>(rec_idx + n4);
-            rec_g = reinterpret_cast<float*>(rec_w + n4);
+        if (TH >= 1 && n_bands <= 32 && (reinterpret_cast<uintptr_t>(scratch) & 15) == 0) {
+            env_bwd_layout(scratch, scratch_bytes, F, &w);
+            if (w.fits) { rec_idx = w.rec_idx; rec_w = w.rec_w; rec_g = w.rec_g; }
         }
     }
     if (mode == 0)
@@ -864,17 +896,12 @@ IA_EXPORT int ia_pbr_shade_bwd(int mode, int64_t F, const float* normal, const f
                 (void)hipGetLastError();
                 attr64 = true;
             }
-            const size_t n4 = ((size_t)F + 3) & ~(size_t)3;
             const int n_tiles = (int)((F + ENV_TILE - 1) / ENV_TILE);
-            char* p = reinterpret_cast<char*>(scratch) + n4 * 24 + 64;
-            EnvRec* sorted = reinterpret_cast<EnvRec*>(p);                 p += n4 * 24;
-            int32_t* counts = reinterpret_cast<int32_t*>(p);               p += (size_t)32 * n_tiles * 4 + 64;
-            int32_t* offs = reinterpret_cast<int32_t*>(p);                 p += (size_t)32 * n_tiles * 4 + 64;
-            int32_t* total = reinterpret_cast<int32_t*>(p);
-            uint32_t* gmax = reinterpret_cast<uint32_t*>(p + 16);          p += 64;
-            void* scan_tmp = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(p) + 255) & ~(uintptr_t)255);
-            p = reinterpret_cast<char*>(scan_tmp) + ia_scan_tmp_bytes((int64_t)(32 * (int64_t)n_tiles));
-            unsigned long long* acc64 = reinterpret_cast<unsigned long long*>((reinterpret_cast<uintptr_t>(p) + 255) & ~(uintptr_t)255);
+            EnvRec* sorted = w.sorted;
+            int32_t *counts = w.counts, *offs = w.offs, *total = w.total;
+            uint32_t* gmax = w.gmax;
+            void* scan_tmp = w.scan_tmp;
+            unsigned long long* acc64 = w.acc64;
             const int64_t n_img = (int64_t)env_h * env_w * 3;
             int fx_shift = 62;                                          // 62 - ceil(log2 F): see env_fixed_scale
             for (int64_t f = 1; f < F; f <<= 1) fx_shift--;

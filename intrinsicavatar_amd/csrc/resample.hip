@@ -118,21 +118,37 @@ struct RsScratch {
     int32_t* first;
 };
 
-constexpr size_t rs_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
+// measured (tmp == nullptr) and carved by the same code; any alignment of tmp
 size_t rs_layout(void* tmp, int64_t n_rays, int64_t n_in, int n, RsScratch* s)
 {
-    char* b = reinterpret_cast<char*>(tmp);
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char* p = b ? b + o : nullptr; o += rs_align(bytes); return p; };
-    float* utab = reinterpret_cast<float*>(take(sizeof(float) * (size_t)(n + 2)));
-    float* cdf = reinterpret_cast<float*>(take(sizeof(float) * (size_t)(n_in + 1)));
-    float* cmax = reinterpret_cast<float*>(take(sizeof(float) * (size_t)(n_in + 1)));
-    ia_rs_ray* ray = reinterpret_cast<ia_rs_ray*>(take(sizeof(ia_rs_ray) * (size_t)(n_rays + 1)));
-    int32_t* rank2ray = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * (size_t)(n_rays + 1)));
-    int32_t* first = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * (size_t)(n_in + 1)));
-    if (s) { s->utab = utab; s->cdf = cdf; s->cmax = cmax; s->ray = ray; s->rank2ray = rank2ray; s->first = first; }
-    return o;
+    ia::Carver c(tmp);
+    RsScratch r;
+    r.utab = c.take<float>((size_t)(n + 2));
+    r.cdf = c.take<float>((size_t)(n_in + 1));
+    r.cmax = c.take<float>((size_t)(n_in + 1));
+    r.ray = c.take<ia_rs_ray>((size_t)(n_rays + 1));
+    r.rank2ray = c.take<int32_t>((size_t)(n_rays + 1));
+    r.first = c.take<int32_t>((size_t)(n_in + 1));
+    c.align_to(256);
+    if (s) *s = r;
+    return c.need(1);
+}
+
+// ia_pack_info / ia_resample_packed_info: per-ray counts, their exclusive scan, the scan's own work area; tmp 4-byte aligned
+struct PackScratch {
+    int32_t* cnt;
+    int32_t* start;
+    void* scan_tmp;
+};
+
+size_t pack_layout(void* tmp, int64_t n_rays, PackScratch* s)
+{
+    ia::Carver c(tmp);
+    s->cnt = c.take<int32_t>((size_t)n_rays, 4);
+    s->start = c.take<int32_t>((size_t)n_rays, 4);
+    s->scan_tmp = c.take<char>((size_t)ia_scan_tmp_bytes(n_rays), 16);
+    c.skip(128);                                          // tail slack, as the callers have always allocated
+    return c.need(4);
 }
 
 // the launch's sample positions: n serial fp32 additions, once (every ray of the reference repeats them)
@@ -454,14 +470,21 @@ __global__ __launch_bounds__(THREADS) void fg_compact_kernel(int64_t n_rays, con
 
 }  // namespace
 
+IA_EXPORT int64_t ia_pack_info_tmp_bytes(int64_t n_rays)
+{
+    PackScratch w;
+    return (int64_t)pack_layout(nullptr, n_rays > 0 ? n_rays : 0, &w);
+}
+
 IA_EXPORT int ia_resample_packed_info(int64_t n_rays, const int32_t* packed_info, int n, int add_steps,
                                       int32_t* resample_packed_info, int32_t* total, void* tmp, ia_stream_t stream)
 {
     hipStream_t s = (hipStream_t)stream;
     if (n_rays == 0) return ia_exclusive_scan_i32(nullptr, nullptr, total, 0, tmp, stream);
-    int32_t* cnt = (int32_t*)tmp;
-    int32_t* start = cnt + n_rays;
-    void* scan_tmp = (void*)(((uintptr_t)(start + n_rays) + 15) & ~(uintptr_t)15);
+    PackScratch w;
+    pack_layout(tmp, n_rays, &w);
+    int32_t *cnt = w.cnt, *start = w.start;
+    void* scan_tmp = w.scan_tmp;
     const int grid = ia::cdiv(n_rays, THREADS);
     resample_counts_kernel<<<grid, THREADS, 0, s>>>(n_rays, packed_info, n, add_steps, cnt);
     int r = ia_exclusive_scan_i32(cnt, start, total, n_rays, scan_tmp, stream);
@@ -475,9 +498,10 @@ IA_EXPORT int ia_pack_info(int64_t n_samples, const int64_t* ray_indices, int64_
 {
     hipStream_t s = (hipStream_t)stream;
     if (n_rays == 0) return IA_OK;
-    int32_t* cnt = (int32_t*)tmp;
-    int32_t* start = cnt + n_rays;
-    void* scan_tmp = (void*)(((uintptr_t)(start + n_rays) + 15) & ~(uintptr_t)15);
+    PackScratch w;
+    pack_layout(tmp, n_rays, &w);
+    int32_t *cnt = w.cnt, *start = w.start;
+    void* scan_tmp = w.scan_tmp;
     hipError_t e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * n_rays, s);
     if (e != hipSuccess) { ia::set_error("ia_pack_info: memset failed"); return IA_ERR_LAUNCH; }
     if (n_samples > 0)
@@ -513,9 +537,7 @@ IA_EXPORT int ia_unpack_data(int64_t n_rays, const int32_t* packed_info, int dat
     return ia::check_launch("ia_unpack_data");
 }
 
-IA_EXPORT size_t ia_resample_tmp_bytes(int64_t n_rays, int64_t n_in, int n) { return rs_layout(nullptr, n_rays, n_in, n, nullptr) + 256; }
-
-static void* rs_aligned(void* tmp) { return (void*)(((uintptr_t)tmp + 255) & ~(uintptr_t)255); }
+IA_EXPORT size_t ia_resample_tmp_bytes(int64_t n_rays, int64_t n_in, int n) { return rs_layout(nullptr, n_rays, n_in, n, nullptr); }
 
 IA_EXPORT int ia_ray_resampling(int64_t n_rays, int64_t n_in, int n, const int32_t* packed_info, const float* starts, const float* ends,
                                 const float* weights, const float* sdfs, const int32_t* resample_packed_info, int64_t n_out,
@@ -541,7 +563,7 @@ IA_EXPORT int ia_ray_resampling_upto(int64_t n_rays, int64_t n_in, int n, const 
     IA_REQUIRE(tmp != nullptr, "ia_ray_resampling: tmp (ia_resample_tmp_bytes) is required");
     hipStream_t st = (hipStream_t)stream;
     RsScratch s;
-    rs_layout(rs_aligned(tmp), n_rays, n_in, n, &s);
+    rs_layout(tmp, n_rays, n_in, n, &s);
     rs_utab_kernel<<<1, 64, 0, st>>>(n, 0, s.utab);
     rs1_rays_kernel<<<ia::cdiv(n_rays, THREADS), THREADS, 0, st>>>(n_rays, n, packed_info, resample_packed_info, starts, ends, weights, sdfs, s,
                                                                    surface_idx, resample_fg_counts, resample_bg_counts);
@@ -562,7 +584,7 @@ IA_EXPORT int ia_ray_resampling_merge(int64_t n_rays, int64_t n_in, int n, const
     IA_REQUIRE(tmp != nullptr, "ia_ray_resampling_merge: tmp (ia_resample_tmp_bytes) is required");
     hipStream_t st = (hipStream_t)stream;
     RsScratch s;
-    rs_layout(rs_aligned(tmp), n_rays, n_in, n, &s);
+    rs_layout(tmp, n_rays, n_in, n, &s);
     rs_utab_kernel<<<1, 64, 0, st>>>(n, 0, s.utab);
     rs2_rays_kernel<<<ia::cdiv(n_rays, THREADS), THREADS, 0, st>>>(n_rays, n, packed_info, vals, is_left, is_right, weights, s);
     rs2_edges_kernel<<<ia::cdiv(n_rays, RS2_TILE), THREADS, 0, st>>>(n_rays, packed_info, resample_packed_info, vals, is_left, is_right, s,
@@ -584,7 +606,7 @@ IA_EXPORT int ia_ray_resampling_merge_count(int64_t n_rays, int64_t n_in, int n,
     IA_REQUIRE(tmp != nullptr, "ia_ray_resampling_merge_count: tmp (ia_resample_tmp_bytes) is required");
     hipStream_t st = (hipStream_t)stream;
     RsScratch s;
-    rs_layout(rs_aligned(tmp), n_rays, n_in, n, &s);
+    rs_layout(tmp, n_rays, n_in, n, &s);
     const int grid = ia::cdiv(n_rays, THREADS);
     rs_utab_kernel<<<1, 64, 0, st>>>(n, 0, s.utab);
     rs2_rays_kernel<<<grid, THREADS, 0, st>>>(n_rays, n, packed_info, vals, is_left, is_right, weights, s);
@@ -602,7 +624,7 @@ IA_EXPORT int ia_ray_resampling_merge_fill(int64_t n_rays, int64_t n_in, int n, 
     if (n_rays == 0) return IA_OK;
     IA_REQUIRE(tmp != nullptr, "ia_ray_resampling_merge_fill: tmp of the matching ia_ray_resampling_merge_count call is required");
     RsScratch s;
-    rs_layout(rs_aligned(tmp), n_rays, n_in, n, &s);
+    rs_layout(tmp, n_rays, n_in, n, &s);
     rs2_compact_kernel<<<ia::cdiv(n_rays, RS2_TILE), THREADS, 0, (hipStream_t)stream>>>(n_rays, packed_info, cnt, start, vals, is_left, is_right,
                                                                                        s, out_vals, out_is_left, out_is_right,
                                                                                        out_ray_indices, out_packed_info);
@@ -632,7 +654,7 @@ static int launch_fine(int64_t n_rays, int64_t n_in, int n, const int32_t* packe
     if (tmp == nullptr) { ia::set_error("%s: tmp (ia_resample_tmp_bytes) is required", what); return IA_ERR_INVALID; }
     if (!(n_out >= 0 && n_out < ((int64_t)1 << 31) && n_out % n == 0)) { ia::set_error("%s: n_out must be n x (rays with samples), below 2^31", what); return IA_ERR_INVALID; }
     RsScratch s;
-    rs_layout(rs_aligned(tmp), n_rays, n_in, n, &s);
+    rs_layout(tmp, n_rays, n_in, n, &s);
     rs_utab_kernel<<<1, 64, 0, st>>>(n, 1, s.utab);
     rs34_rays_kernel<SDF><<<grid, THREADS, 0, st>>>(n_rays, n, packed_info, rpi, wa, sdfs, s);
     if (n_out > 0)

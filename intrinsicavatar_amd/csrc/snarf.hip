@@ -1747,29 +1747,55 @@ IA_EXPORT int ia_spec_rows_slots(void) { return SPEC_ROOTS; }
 
 extern "C" int ia_exclusive_scan_i32(const int32_t* in, int32_t* out, int32_t* total, int64_t n, void* tmp, ia_stream_t stream);
 
-// scratch of the rows search: [overflow count | flagged count | pad] [rec: cap x 3 int32] [x: cap x 3 float] [keep: cap bytes]
-// [flagged: point (int32) | valid mask (uint32) | x (16 x 3 float)] x SPEC_FLAG_CAP
+// scratch of the rows search: [overflow count | flagged count] [rec: cap x 3 int32] [x: cap x 3 float] [keep: cap bytes]
+// [flagged: point (int32) | valid mask (uint32) | x (16 x 3 float)] x spec_flag_cap(N); scratch 8-byte aligned
 static const int SPEC_OVF_CAP = 1 << 18;
-static const size_t SPEC_OVF_BYTES = 64 + (size_t)SPEC_OVF_CAP * (12 + 12 + 1) + 64;
-IA_EXPORT size_t ia_spec_rows_overflow_bytes(int64_t N) { return SPEC_OVF_BYTES + (size_t)spec_flag_cap(N) * (4 + 4 + 16 * 12) + 64; }
 
 struct OvfLayout { int32_t* count; int32_t* rec; float* x; uint8_t* keep; SpecFlag flag; };
-static OvfLayout ovf_layout(void* scratch, int64_t N)
+static size_t ovf_layout(void* scratch, int64_t N, OvfLayout* L)
 {
-    const int64_t fcap = spec_flag_cap(N);
-    char* b = reinterpret_cast<char*>(scratch);
+    const size_t fcap = (size_t)spec_flag_cap(N);
+    ia::Carver c(scratch);
+    L->count = c.take<int32_t>(2, 64);
+    L->rec = c.take<int32_t>((size_t)SPEC_OVF_CAP * 3, 64);
+    L->x = c.take<float>((size_t)SPEC_OVF_CAP * 3, 64);
+    L->keep = c.take<uint8_t>((size_t)SPEC_OVF_CAP, 64);
+    c.skip(64);
+    L->flag.count = L->count ? L->count + 1 : nullptr;
+    L->flag.point = c.take<int32_t>(fcap, 64);
+    L->flag.valid = c.take<uint32_t>(fcap, 64);
+    L->flag.x = c.take<float>(fcap * 16 * 3, 64);
+    c.skip(64);                                          // tail slack, as the callers have always allocated
+    L->flag.cap = (int)fcap;
+    return c.need(8);
+}
+
+IA_EXPORT size_t ia_spec_rows_overflow_bytes(int64_t N)
+{
     OvfLayout L;
-    L.count = reinterpret_cast<int32_t*>(b);
-    L.rec = reinterpret_cast<int32_t*>(b + 64);
-    L.x = reinterpret_cast<float*>(b + 64 + (size_t)SPEC_OVF_CAP * 12);
-    L.keep = reinterpret_cast<uint8_t*>(b + 64 + (size_t)SPEC_OVF_CAP * 24);
-    char* f = b + ((SPEC_OVF_BYTES + 63) & ~(size_t)63);
-    L.flag.count = reinterpret_cast<int32_t*>(b) + 1;
-    L.flag.point = reinterpret_cast<int32_t*>(f);
-    L.flag.valid = reinterpret_cast<uint32_t*>(f + (size_t)fcap * 4);
-    L.flag.x = reinterpret_cast<float*>(f + (size_t)fcap * 8);
-    L.flag.cap = (int)fcap;
-    return L;
+    return ovf_layout(nullptr, N, &L);
+}
+
+// ia_deform_rows_pack_split: the tiles' counts of first candidates + the work area of their scan; scan_tmp 8-byte aligned
+struct PackSplitTmp {
+    int32_t* sums;
+    void* scan_tmp;
+    int64_t tiles;
+};
+static size_t pack_split_layout(void* tmp, int64_t N, PackSplitTmp* t)
+{
+    t->tiles = (N + FIRST_TILE - 1) / FIRST_TILE;
+    ia::Carver c(tmp);
+    t->sums = c.take<int32_t>((size_t)t->tiles);
+    t->scan_tmp = c.take<char>((size_t)ia_scan_tmp_bytes(t->tiles));
+    c.skip(1024);                                          // tail slack, as the callers have always allocated
+    return c.need(8);
+}
+
+IA_EXPORT int64_t ia_deform_rows_pack_split_tmp_bytes(int64_t N)
+{
+    PackSplitTmp t;
+    return (int64_t)pack_split_layout(nullptr, N > 0 ? N : 0, &t);
 }
 
 // total_and_overflow [1] <- max(flagged points / their capacity, overflow records / their capacity) scaled to the flagged capacity:
@@ -1787,7 +1813,8 @@ IA_EXPORT int ia_fuse_broyden_spec_rows(int64_t N, int I, const float* xd_tgt, c
 {
     IA_REQUIRE(N * I < ((int64_t)1 << 31), "ia_fuse_broyden_spec_rows: N * I must stay below 2^31");
     hipStream_t s = (hipStream_t)stream;
-    OvfLayout o = ovf_layout(ovf_scratch, N);
+    OvfLayout o;
+    ovf_layout(ovf_scratch, N, &o);
     ia::zero_bytes(o.count, 2 * sizeof(int32_t), s);
     if (N == 0) {
         ia::zero_bytes(total_and_overflow, 2 * sizeof(int32_t), s);
@@ -1833,7 +1860,8 @@ IA_EXPORT int ia_deform_rows_pack(int64_t N, int I, const float* x_rows, const i
     if (N == 0) return IA_OK;
     IA_REQUIRE(cand_x != x_rows, "ia_deform_rows_pack: cand_x must not alias x_rows");
     IA_REQUIRE((norm_center == nullptr) == (norm_scale == nullptr), "ia_deform_rows_pack: norm_center and norm_scale go together");
-    OvfLayout o = ovf_layout(const_cast<void*>(ovf_scratch), N);
+    OvfLayout o;
+    ovf_layout(const_cast<void*>(ovf_scratch), N, &o);
     rows_pack_kernel<<<ia::cdiv(N, THREADS), THREADS, 0, (hipStream_t)stream>>>(N, I, x_rows, cnt, meta, start, ovf_head, o.rec, o.x, o.keep,
                                                                                 cand_x, cand_src, norm_center, norm_scale);
     return ia::check_launch("ia_deform_rows_pack");
@@ -1842,7 +1870,7 @@ IA_EXPORT int ia_deform_rows_pack(int64_t N, int I, const float* x_rows, const i
 // ia_deform_rows_pack in the SPLIT layout (rows_pack_kernel).  Outputs for the reader (ia_deform_select_min_split): first_pos [N] int32 =
 // exclusive count of points that have candidates INSIDE the point's tile of 1024, first_tile_off [ceil(N / 1024)] int32 = the tiles' offsets,
 // n_first [1] int32 (DEVICE) = the number of such points; the first candidate of p sits at first_pos[p] + first_tile_off[p / 1024], its other
-// candidates from n_first on, point-major.  scan_tmp: ia_scan_tmp_bytes(N / 1024 + 1) + 4 (N / 1024 + 1) + 512 bytes.
+// candidates from n_first on, point-major.  scan_tmp: ia_deform_rows_pack_split_tmp_bytes(N) bytes.
 IA_EXPORT int ia_deform_rows_pack_split(int64_t N, int I, const float* x_rows, const int32_t* cnt, const uint32_t* meta, const int32_t* start,
                                         const int32_t* ovf_head, const void* ovf_scratch, int32_t* first_pos, int32_t* first_tile_off,
                                         int32_t* n_first, float* cand_x, const float* norm_center, const float* norm_scale, void* scan_tmp,
@@ -1855,13 +1883,16 @@ IA_EXPORT int ia_deform_rows_pack_split(int64_t N, int I, const float* x_rows, c
     IA_REQUIRE(first_pos != nullptr && first_tile_off != nullptr && n_first != nullptr && scan_tmp != nullptr,
                "ia_deform_rows_pack_split: first_pos, first_tile_off, n_first and scan_tmp are required");
     hipStream_t s = (hipStream_t)stream;
-    const int64_t tiles = (N + FIRST_TILE - 1) / FIRST_TILE;
-    int32_t* sums = reinterpret_cast<int32_t*>(scan_tmp);
-    void* tmp = reinterpret_cast<char*>(scan_tmp) + (((size_t)tiles * 4 + 255) & ~(size_t)255);
+    PackSplitTmp t;
+    pack_split_layout(scan_tmp, N, &t);
+    const int64_t tiles = t.tiles;
+    int32_t* sums = t.sums;
+    void* tmp = t.scan_tmp;
     first_scan_tiles_kernel<<<(int)tiles, 256, 0, s>>>(N, cnt, first_pos, sums);
     const int r = ia_exclusive_scan_i32(sums, first_tile_off, n_first, tiles, tmp, stream);
     if (r != IA_OK) return r;
-    OvfLayout o = ovf_layout(const_cast<void*>(ovf_scratch), N);
+    OvfLayout o;
+    ovf_layout(const_cast<void*>(ovf_scratch), N, &o);
     rows_pack_kernel<<<ia::cdiv(N, THREADS), THREADS, 0, s>>>(N, I, x_rows, cnt, meta, start, ovf_head, o.rec, o.x, o.keep, cand_x, nullptr,
                                                               norm_center, norm_scale, first_pos, first_tile_off, n_first);
     return ia::check_launch("ia_deform_rows_pack_split");

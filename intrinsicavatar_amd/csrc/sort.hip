@@ -62,8 +62,6 @@ __global__ __launch_bounds__(THREADS) void scatter_rows3_i32_kernel(int64_t n, c
     dst[3 * j] = src[3 * i]; dst[3 * j + 1] = src[3 * i + 1]; dst[3 * j + 2] = src[3 * i + 2];
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // ---- the radix sort -------------------------------------------------------------------------------------------------------------
 // measured on the MI355X (tools/sort_probe.py, 18 M / 40 M / 140 M march points, ms per sort; -DIA_SORT_THREADS / -DIA_SORT_BITS builds):
 //   rocPRIM onesweep (rounds 2-4)                  0.732 / 1.394 / 4.449
@@ -387,27 +385,44 @@ __global__ __launch_bounds__(ST) void radix_scatter_kernel(int64_t n, const uint
     }
 }
 
+// the passes of one sort and its work area: two pair columns (8 B per element; the key column of pass 0 lives in the second one, which
+// pass 0 does not write) | per-tile histograms | their offsets | chunk sums, chunk offsets, digit bases of the histogram scan; tmp
+// 256-byte aligned
 struct SortPlan {
     int npass, bits[4], shift[4];
-    int ntiles;
-    size_t col, hist_bytes, scan_bytes;
+    int ntiles, nchunks;
+    uint2* pbuf[2];
+    uint32_t* keys0;
+    int32_t *hist, *offs, *chunk_sum, *chunk_off, *digit_base;
+    bool fits;
 };
 
-SortPlan sort_plan(int64_t n, int drop_bits)
+size_t sort_layout(void* tmp, size_t bytes, int64_t n, int drop_bits, SortPlan* p)
 {
-    SortPlan p;
     const int nbits = 30 - drop_bits;
-    p.npass = (nbits + MAXB - 1) / MAXB;
+    p->npass = (nbits + MAXB - 1) / MAXB;
     int left = nbits, sh = drop_bits;
-    for (int k = 0; k < p.npass; k++) {
-        const int b = (left + (p.npass - k) - 1) / (p.npass - k);      // as even as possible: 10 10 10, 9 9 9, 8 8 8
-        p.bits[k] = b; p.shift[k] = sh; sh += b; left -= b;
+    for (int k = 0; k < p->npass; k++) {
+        const int b = (left + (p->npass - k) - 1) / (p->npass - k);      // as even as possible: 10 10 10, 9 9 9, 8 8 8
+        p->bits[k] = b; p->shift[k] = sh; sh += b; left -= b;
     }
-    p.ntiles = (int)((n + TILE - 1) / TILE);
-    p.col = align256((size_t)n * 4);
-    p.hist_bytes = align256((size_t)NBMAX * (size_t)p.ntiles * 4);
-    p.scan_bytes = align256((size_t)NBMAX * (size_t)(2 * ((p.ntiles + SCAN_CHUNK - 1) / SCAN_CHUNK) + 1) * 4);
-    return p;
+    p->ntiles = (int)((n + TILE - 1) / TILE);
+    p->nchunks = (p->ntiles + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    ia::Carver c(tmp, bytes);
+    for (int k = 0; k < 2; k++) {                       // a pair column = two 256-byte aligned halves of n words each
+        p->pbuf[k] = reinterpret_cast<uint2*>(c.take<uint32_t>((size_t)n));
+        c.take<uint32_t>((size_t)n);
+    }
+    p->keys0 = reinterpret_cast<uint32_t*>(p->pbuf[1]);
+    p->hist = c.take<int32_t>((size_t)NBMAX * (size_t)p->ntiles);
+    p->offs = c.take<int32_t>((size_t)NBMAX * (size_t)p->ntiles);
+    p->chunk_sum = c.take<int32_t>((size_t)NBMAX * (size_t)p->nchunks);
+    p->chunk_off = c.take<int32_t>((size_t)NBMAX * (size_t)p->nchunks, 4);
+    p->digit_base = c.take<int32_t>((size_t)NBMAX, 4);
+    c.align_to(256);
+    c.skip(256);                                          // tail slack, as the callers have always allocated
+    p->fits = c.fits();
+    return c.need(256);
 }
 
 int g_rank_mode = 0;
@@ -420,9 +435,9 @@ IA_EXPORT int ia_sort_rank_mode(void) { return g_rank_mode; }
 
 IA_EXPORT size_t ia_morton_order_tmp_bytes(int64_t n)
 {
+    SortPlan p;
     if (n <= 0) return 256;
-    const SortPlan p = sort_plan(n, 0);
-    return 4 * p.col + 2 * p.hist_bytes + p.scan_bytes + 256;
+    return sort_layout(nullptr, SIZE_MAX, n, 0, &p);
 }
 
 // order [n] int32: the permutation that lists the points by the Morton code of their cell (cell size 1 / inv_cell, 10 bits per
@@ -433,17 +448,14 @@ IA_EXPORT int ia_morton_order(int64_t n, const float* pts, const float* origin_h
     if (n == 0) return IA_OK;
     IA_REQUIRE(n < ((int64_t)1 << 31), "ia_morton_order: n must stay below 2^31");
     IA_REQUIRE(drop_bits >= 0 && drop_bits < 30, "ia_morton_order: drop_bits out of range");
-    IA_REQUIRE(tmp != nullptr && tmp_bytes >= ia_morton_order_tmp_bytes(n), "ia_morton_order: tmp too small (ia_morton_order_tmp_bytes)");
+    SortPlan p;
+    sort_layout(tmp, tmp_bytes, n, drop_bits, &p);
+    IA_REQUIRE(tmp != nullptr && p.fits, "ia_morton_order: tmp too small (ia_morton_order_tmp_bytes)");
     IA_REQUIRE((reinterpret_cast<uintptr_t>(tmp) & 255) == 0, "ia_morton_order: tmp must be 256-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    const SortPlan p = sort_plan(n, drop_bits);
-    char* base = reinterpret_cast<char*>(tmp);
-    // two pair columns (8 B per element); the key column of pass 0 lives in the second one, which pass 0 does not write
-    uint2* pbuf[2] = {reinterpret_cast<uint2*>(base), reinterpret_cast<uint2*>(base + 2 * p.col)};
-    uint32_t* keys0 = reinterpret_cast<uint32_t*>(base + 2 * p.col);
-    int32_t* hist = reinterpret_cast<int32_t*>(base + 4 * p.col);
-    int32_t* offs = reinterpret_cast<int32_t*>(base + 4 * p.col + p.hist_bytes);
-    void* scan_tmp = base + 4 * p.col + 2 * p.hist_bytes;
+    uint2* const* pbuf = p.pbuf;
+    uint32_t* keys0 = p.keys0;
+    int32_t *hist = p.hist, *offs = p.offs;
     static const int raster = getenv("IA_SORT_RASTER_BITS") ? atoi(getenv("IA_SORT_RASTER_BITS")) : 0;       // experiment knob, see morton_key
     const size_t lds = (size_t)2 * TILE * sizeof(uint32_t);
     // once per DEVICE: 2 x TILE x 4 = 128 KB of dynamic LDS per workgroup of the scatter kernels (above the 64 KB a kernel gets without the
@@ -494,10 +506,8 @@ IA_EXPORT int ia_morton_order(int64_t n, const float* pts, const float* origin_h
                                                              p.shift[k], p.bits[k], hist, p.ntiles, raster);
         else
             radix_count_kernel<false><<<p.ntiles, CT, 0, s>>>(n, nullptr, 0.f, 0.f, 0.f, 0.f, nullptr, pin, p.shift[k], p.bits[k], hist, p.ntiles, 0);
-        const int nchunks = (p.ntiles + SCAN_CHUNK - 1) / SCAN_CHUNK;
-        int32_t* chunk_sum = reinterpret_cast<int32_t*>(scan_tmp);
-        int32_t* chunk_off = chunk_sum + (size_t)NBMAX * nchunks;
-        int32_t* digit_base = chunk_off + (size_t)NBMAX * nchunks;
+        const int nchunks = p.nchunks;
+        int32_t *chunk_sum = p.chunk_sum, *chunk_off = p.chunk_off, *digit_base = p.digit_base;
         radix_chunk_sums_kernel<<<nchunks, 256, 0, s>>>(hist, nb, p.ntiles, chunk_sum);
         radix_chunk_bases_kernel<<<1, 1024, 0, s>>>(chunk_sum, nb, nchunks, chunk_off, digit_base);
         radix_chunk_apply_kernel<<<nchunks, 256, 0, s>>>(hist, nb, p.ntiles, chunk_off, digit_base, offs);

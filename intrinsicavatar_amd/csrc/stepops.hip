@@ -567,7 +567,26 @@ IA_EXPORT int ia_sg_image_bwd(int K, int H, int W, const float* axis, const floa
     return ia::check_launch("ia_sg_image_bwd");
 }
 
-IA_EXPORT int64_t ia_envlight_pdf_tables_tmp_bytes(int H, int W) { return 2 * (int64_t)(((int64_t)H * W + PDF_TILE - 1) / PDF_TILE) * 8 + 64; }
+// per-tile sums of the weights and of the pmf; tmp 8-byte aligned
+struct PdfTablesTmp {
+    double *tile_sum, *tile_pmf;
+};
+
+static size_t pdf_tables_layout(void* tmp, int64_t n_tiles, PdfTablesTmp* t)
+{
+    ia::Carver c(tmp);
+    t->tile_sum = c.take<double>((size_t)n_tiles, 8);
+    t->tile_pmf = c.take<double>((size_t)n_tiles, 8);
+    c.skip(64);                                          // tail slack, as the callers have always allocated
+    return c.need(8);
+}
+
+IA_EXPORT int64_t ia_envlight_pdf_tables_tmp_bytes(int H, int W)
+{
+    PdfTablesTmp t;
+    const int64_t P = (int64_t)H * W;
+    return (int64_t)pdf_tables_layout(nullptr, P > 0 ? (P + PDF_TILE - 1) / PDF_TILE : 0, &t);
+}
 
 IA_EXPORT int ia_envlight_pdf_tables(int H, int W, const float* base, float* pmf, double* cdf, void* tmp, ia_stream_t stream)
 {
@@ -576,8 +595,9 @@ IA_EXPORT int ia_envlight_pdf_tables(int H, int W, const float* base, float* pmf
     IA_REQUIRE(P64 < ((int64_t)1 << 30), "image too large");
     const int P = (int)P64, n_tiles = (P + PDF_TILE - 1) / PDF_TILE;
     IA_REQUIRE(n_tiles <= 4096, "at most 4096 tiles of 1024 texels (larger images: the caller's own reduction)");
-    double* tile_sum = (double*)tmp;
-    double* tile_pmf = tile_sum + n_tiles;
+    PdfTablesTmp t;
+    pdf_tables_layout(tmp, n_tiles, &t);
+    double *tile_sum = t.tile_sum, *tile_pmf = t.tile_pmf;
     hipStream_t s = (hipStream_t)stream;
     envlight_w_kernel<<<n_tiles, 256, 0, s>>>(P, W, H, base, cdf, tile_sum);
     envlight_pmf_kernel<<<n_tiles, 256, 0, s>>>(P, n_tiles, tile_sum, cdf, pmf, tile_pmf);

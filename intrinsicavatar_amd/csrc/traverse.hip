@@ -1059,10 +1059,26 @@ IA_EXPORT int ia_traverse_grids_fill(int64_t n_rays, const float* rays_o, const 
     return ia::check_launch("ia_traverse_grids_fill");
 }
 
+// look-back state of the single-launch traversal: one word per tile of rays (+ 1) and the tile ticket; scratch 8-byte aligned.  Sized and
+// zeroed (whole, slack included) for tiles of TR_THREADS rays; the span-sorted variant has fewer, larger tiles and carves a prefix of it.
+struct FusedScratch {
+    uint64_t* state;
+    uint32_t* ticket;
+};
+
+static size_t fused_layout(void* scratch, int64_t tiles, FusedScratch* w)
+{
+    ia::Carver c(scratch);
+    w->state = c.take<uint64_t>((size_t)tiles + 1, 8);
+    w->ticket = c.take<uint32_t>(2, 4);
+    c.skip(64);
+    return c.need(8);
+}
+
 IA_EXPORT int64_t ia_traverse_fused_scratch_bytes(int64_t n_rays)
 {
-    const int64_t tiles = (n_rays + TR_THREADS - 1) / TR_THREADS;
-    return (tiles + 2) * 8 + 64;
+    FusedScratch w;
+    return (int64_t)fused_layout(nullptr, n_rays > 0 ? ia::cdiv(n_rays, TR_THREADS) : 0, &w);
 }
 
 IA_EXPORT int ia_traverse_grids_fused(int64_t n_rays, const float* rays_o, const float* rays_d,
@@ -1089,8 +1105,9 @@ IA_EXPORT int ia_traverse_grids_fused(int64_t n_rays, const float* rays_o, const
         (void)hipGetLastError();
         attr_set = true;
     }
-    const int64_t sb = ia_traverse_fused_scratch_bytes(n_rays);
-    ia::zero_bytes(scratch, ((size_t)sb + 3) & ~(size_t)3, s);
+    const int tiles = ia::cdiv(n_rays, TR_THREADS);
+    FusedScratch w;
+    ia::zero_bytes(scratch, fused_layout(scratch, tiles, &w), s);
     // span-sorted tiles (1024 rays on 512 lanes): for INCOHERENT batches -- the secondary march: 10.7 -> 8.6 ms per headline step.
     // Coherent primary rays and dense grids are faster in ray order (85 vs 95 us per 540x540 frame; 238 vs 290 us on a dense
     // grid, where the walk is short and the expansion dominates), so the caller chooses; env IA_TRAVERSE_TILES = ray | span
@@ -1109,8 +1126,11 @@ IA_EXPORT int ia_traverse_grids_fused(int64_t n_rays, const float* rays_o, const
                 attr2 = true;
             }
             const int tiles_s = ia::cdiv(n_rays, ST_RAYS);
-            uint64_t* state_s = (uint64_t*)scratch;
-            uint32_t* ticket_s = (uint32_t*)(state_s + tiles_s + 1);
+            static_assert(ST_RAYS >= TR_THREADS, "the span-sorted tiles fit the area sized for tiles of TR_THREADS rays");
+            FusedScratch ws;
+            fused_layout(scratch, tiles_s, &ws);
+            uint64_t* state_s = ws.state;
+            uint32_t* ticket_s = ws.ticket;
             const float inv_bin = (float)(62.0 / (max_steps * (double)step_size));
             const int grid_s = tiles_s < 512 ? tiles_s : 512;      // 2 resident workgroups per CU
             traverse_sorted_kernel<<<grid_s, ST_THREADS, lds, s>>>(
@@ -1120,9 +1140,8 @@ IA_EXPORT int ia_traverse_grids_fused(int64_t n_rays, const float* rays_o, const
             return ia::check_launch("ia_traverse_grids_fused");
         }
     }
-    const int tiles = ia::cdiv(n_rays, TR_THREADS);
-    uint64_t* state = (uint64_t*)scratch;
-    uint32_t* ticket = (uint32_t*)(state + tiles + 1);
+    uint64_t* state = w.state;
+    uint32_t* ticket = w.ticket;
     const int grid = tiles < 768 ? tiles : 768;        // 3 resident workgroups per CU (53 KB of LDS each)
     traverse_fused_kernel<<<grid, TR_THREADS, lds, s>>>(
         n_rays, rays_o, rays_d, grid_bits, rx, ry, rz, aabb, near_planes, far_planes, step_size, cone_angle, state, ticket,

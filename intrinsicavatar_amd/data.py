@@ -196,7 +196,7 @@ class TrainingFrames:
         lib, dev = L.lib(), self.device
         with torch.cuda.device(dev):
             st = L.stream()
-            scratch = torch.empty(int(lib.ia_flag_lists_scratch_bytes(L.i64(F), L.i64(N))) + 64, dtype=torch.uint8, device=dev)
+            scratch = L.work_area(lib.ia_flag_lists_scratch_bytes(L.i64(F), L.i64(N)), dev)
             totals = torch.empty(2, dtype=torch.int32, device=dev)
             args = (L.i64(F), L.i64(N), L.ptr(self.masks), L.ptr(mask_i), L.ptr(mask_o), L.ptr(scratch))
             L.check(lib.ia_flag_lists_count(*args, L.ptr(totals), st), "ia_flag_lists_count")

@@ -212,17 +212,17 @@ class SNARFDeformer:
         src = torch.empty(P * I, dtype=torch.int32, device=dev) if with_src else None
         if os.environ.get("IA_PACK", "tiles") == "lookback":
             nbytes = int(lib.ia_deform_filter_compact_tmp_bytes(L.i64(P)))
-            tmp = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+            tmp = L.work_area(nbytes, dev)
             L.check(lib.ia_deform_filter_compact(L.i64(P), L.i32(I), L.ptr(x), L.ptr(valid), L.ptr(cnt), L.ptr(start), L.ptr(x),
-                                                 L.ptr(src), L.ptr(None), L.ptr(total), L.ptr(tmp), C.c_size_t(tmp.numel() * 8), st),
+                                                 L.ptr(src), L.ptr(None), L.ptr(total), L.ptr(tmp), C.c_size_t(nbytes), st),
                     "ia_deform_filter_compact")
             Q = int(total.item())
             self._check_voxels()
             return x.reshape(-1, 3)[:Q], (src[:Q] if with_src else None), cnt, start, Q
         nbytes = int(lib.ia_deform_filter_tiles_tmp_bytes(L.i64(P)))
-        tmp = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        tmp = L.work_area(nbytes, dev)
         L.check(lib.ia_deform_filter_tiles(L.i64(P), L.i32(I), L.ptr(x), L.ptr(valid), L.ptr(cnt), L.ptr(start), L.ptr(src), L.ptr(None),
-                                           L.ptr(total), L.ptr(tmp), C.c_size_t(tmp.numel() * 8), st), "ia_deform_filter_tiles")
+                                           L.ptr(total), L.ptr(tmp), C.c_size_t(nbytes), st), "ia_deform_filter_tiles")
         Q = int(total.item())
         self._check_voxels()
         cand_x = torch.empty((Q, 3), device=dev)
@@ -266,7 +266,7 @@ class SNARFDeformer:
         cnt, meta, start, ovf_head = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(4))
         # overflow records + the list of points the kernel redoes with the filter off (1 / 64 of the batch): a grow-only work area
         # (locals, not attributes: concurrent calls on several streams -- render.compute_indirect_radiance -- each have their own)
-        ovf_scratch = L.scratch("spec_rows", int(lib.ia_spec_rows_overflow_bytes(L.i64(P))), dev)
+        ovf_scratch = L.work_area(lib.ia_spec_rows_overflow_bytes(L.i64(P)), dev, "spec_rows")
         ovf_cap = self._tls.ovf_cap = int(lib.ia_spec_rows_overflow_capacity(L.i64(P)))
         tot = torch.empty(2, dtype=torch.int32, device=dev)
         # IA_SEARCH_TOKEN=1 (experiment, measured without effect -- DESIGN 4.5): one search on the DEVICE at a time; this stream's search
@@ -314,7 +314,7 @@ class SNARFDeformer:
                                                   L.ptr(ovf_scratch), L.ptr(first_pos), L.ptr(tile_off_n), L.ptr(tile_off_n[tiles:]), L.ptr(cand_x),
                                                   L.ptr(normalize[0].contiguous().float() if normalize else None),
                                                   L.ptr(normalize[1].contiguous().float() if normalize else None),
-                                                  L.ptr(L.scan_tmp(tiles + 1, dev, extra_bytes=4 * tiles + 1024)), st), "ia_deform_rows_pack_split")
+                                                  L.ptr(L.work_area(lib.ia_deform_rows_pack_split_tmp_bytes(L.i64(P)), dev)), st), "ia_deform_rows_pack_split")
             return cand_x, None, cnt, start, Q, None, None, (first_pos, tile_off_n[:tiles]), tile_off_n[tiles:]
         cand_src = torch.empty(Q, dtype=torch.int32, device=dev) if with_src else None
         L.check(lib.ia_deform_rows_pack(L.i64(P), L.i32(I), L.ptr(x_rows), L.ptr(cnt), L.ptr(meta), L.ptr(start), L.ptr(ovf_head),

@@ -49,7 +49,7 @@ def hashgrid_forward(x01: Tensor, params: Tensor, cfg=HASH, with_jac: bool = Fal
     method = os.environ.get("IA_HASH_FWD") or ("xcd" if (n >= HASH_FWD_XCD_MIN and not with_jac) else "flat")
     if method == "xcd":
         nb = int(L.lib().ia_hashgrid_fwd_scratch_bytes(L.i64(n), L.i32(cfg["n_levels"]), L.i32(1 if with_jac else 0)))
-        scratch = torch.empty(nb, dtype=torch.uint8, device=x01.device)
+        scratch = L.work_area(nb, x01.device)
         L.check(L.lib().ia_hashgrid_fwd_xcd(L.i64(n), L.ptr(x01), L.ptr(params), L.i32(cfg["n_levels"]),
                                             L.i32(cfg["n_features_per_level"]), L.i32(cfg["log2_hashmap_size"]),
                                             L.i32(cfg["base_resolution"]), L.f32(cfg["per_level_scale"]), L.ptr(out),
@@ -86,7 +86,7 @@ def hashgrid_backward(x01: Tensor, g_enc: Optional[Tensor], grad_params: Tensor,
         m = min(HASH_BWD_CHUNK, n - c0)
         nb = int(L.lib().ia_hashgrid_bwd_scratch_bytes(L.i64(m), L.i32(cfg["n_levels"]), L.i32(cfg["log2_hashmap_size"]),
                                                        L.i32(cfg["base_resolution"]), L.f32(cfg["per_level_scale"])))
-        scratch = torch.empty(nb, dtype=torch.uint8, device=x01.device)
+        scratch = L.work_area(nb, x01.device)
         sl = lambda t: None if t is None else t[c0:c0 + m]      # noqa: E731  (row slices keep stride / contiguity)
         ge, gj = sl(g_enc), sl(g_jac)
         L.check(L.lib().ia_hashgrid_bwd_binned(
@@ -369,7 +369,7 @@ class VolumeSDF(nn.Module):
         cfg = HASH
         xp = points.contiguous() if normalized else normalize_points(points, self.center, self.scale)
         nb = int(L.lib().ia_hashgrid_fwd_scratch_bytes(L.i64(n), L.i32(cfg["n_levels"]), L.i32(0)))
-        scratch = L.scratch("hash_levels", nb, xp.device)
+        scratch = L.work_area(nb, xp.device, "hash_levels")
         L.check(L.lib().ia_hashgrid_fwd_xcd(L.i64(n), L.ptr(xp), L.ptr(self.grid_params), L.i32(cfg["n_levels"]),
                                             L.i32(cfg["n_features_per_level"]), L.i32(cfg["log2_hashmap_size"]),
                                             L.i32(cfg["base_resolution"]), L.f32(cfg["per_level_scale"]), L.ptr(None), L.i32(0),
@@ -398,7 +398,7 @@ class VolumeSDF(nn.Module):
             cfg = HASH
             lib, st = L.lib(), L.stream()
             nb = int(lib.ia_hashgrid_fwd_scratch_bytes(L.i64(n), L.i32(cfg["n_levels"]), L.i32(1)))
-            scratch = L.scratch("hash_levels_jac", nb, xp.device)
+            scratch = L.work_area(nb, xp.device, "hash_levels_jac")
             L.check(lib.ia_hashgrid_fwd_levels(L.i64(n), L.ptr(xp), L.ptr(self.grid_params), L.i32(cfg["n_levels"]),
                                                L.i32(cfg["n_features_per_level"]), L.i32(cfg["log2_hashmap_size"]),
                                                L.i32(cfg["base_resolution"]), L.f32(cfg["per_level_scale"]), L.i32(1), L.ptr(scratch), st),

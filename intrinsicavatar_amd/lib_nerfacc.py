@@ -28,7 +28,7 @@ def _resample_info(packed_info: Tensor, n: int, add_steps: bool, read_total: boo
     dev = packed_info.device
     rpi = torch.empty((n_rays, 2), dtype=torch.int32, device=dev)
     total = torch.empty(1, dtype=torch.int32, device=dev)          # written by the scan
-    tmp = L.scan_tmp(n_rays, dev, extra_bytes=8 * n_rays + 64)
+    tmp = L.work_area(L.lib().ia_pack_info_tmp_bytes(L.i64(n_rays)), dev)
     L.check(L.lib().ia_resample_packed_info(L.i64(n_rays), L.ptr(packed_info), L.i32(n), L.i32(int(add_steps)),
                                             L.ptr(rpi), L.ptr(total), L.ptr(tmp), L.stream()),
             "ia_resample_packed_info")
@@ -43,8 +43,7 @@ def _f32v(t: Tensor, n: Optional[int] = None) -> Tensor:
 
 def _resample_tmp(n_rays: int, n_in: int, n: int, dev) -> Tensor:
     """scratch of one K1..K4 call: u-table, CDF tables, per-ray records (csrc/resample.hip)."""
-    nbytes = int(L.lib().ia_resample_tmp_bytes(L.i64(n_rays), L.i64(n_in), L.i32(n)))
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    return L.work_area(L.lib().ia_resample_tmp_bytes(L.i64(n_rays), L.i64(n_in), L.i32(n)), dev)
 
 
 # ----------------------------------------------------------------------------- K1
@@ -91,7 +90,7 @@ def ray_resampling_capacity(packed_info: Tensor, t_starts: Tensor, t_ends: Tenso
     assert cap < (1 << 31), "n_samples x n_rays must stay below 2^31"
     rpi = torch.empty((n_rays, 2), dtype=torch.int32, device=dev)
     L.check(L.lib().ia_resample_packed_info(L.i64(n_rays), L.ptr(packed_info), L.i32(n_samples), L.i32(0), L.ptr(rpi), L.ptr(total),
-                                            L.ptr(L.scan_tmp(n_rays, dev, extra_bytes=8 * n_rays + 64)), L.stream()), "ia_resample_packed_info")
+                                            L.ptr(L.work_area(L.lib().ia_pack_info_tmp_bytes(L.i64(n_rays)), dev)), L.stream()), "ia_resample_packed_info")
     ts = torch.empty((cap, 1), dtype=torch.float32, device=dev)
     offs = torch.empty((cap, 1), dtype=torch.float32, device=dev)
     idxs = torch.empty((cap,), dtype=torch.int64, device=dev)
@@ -348,7 +347,7 @@ def pack_info(ray_indices: Tensor, n_rays: int = None) -> Tensor:
     ray_indices = ray_indices.contiguous().to(torch.int64)
     dev = ray_indices.device
     out = torch.empty((n_rays, 2), dtype=torch.int32, device=dev)
-    tmp = L.scan_tmp(n_rays, dev, extra_bytes=8 * n_rays + 64)
+    tmp = L.work_area(L.lib().ia_pack_info_tmp_bytes(L.i64(n_rays)), dev)
     L.check(L.lib().ia_pack_info(L.i64(ray_indices.shape[0]), L.ptr(ray_indices), L.i64(n_rays), L.ptr(out),
                                  L.ptr(tmp), L.stream()), "ia_pack_info")
     return out

@@ -46,7 +46,7 @@ def marching_cubes(level: torch.Tensor, threshold: float = 0.0, vmin: Optional[S
     level = level.contiguous()
     nx, ny, nz = (int(s) for s in level.shape)
     lib, st, dev = L.lib(), L.stream(), level.device
-    scratch = torch.empty(int(lib.ia_mc_scratch_bytes(L.i32(nx), L.i32(ny), L.i32(nz))), dtype=torch.uint8, device=dev)
+    scratch = L.work_area(lib.ia_mc_scratch_bytes(L.i32(nx), L.i32(ny), L.i32(nz)), dev)
     totals = torch.empty(2, dtype=torch.int64, device=dev)
     thr = L.f32(float(threshold))
     L.check(lib.ia_mc_count(L.i32(nx), L.i32(ny), L.i32(nz), L.ptr(level), thr, L.ptr(scratch), L.ptr(totals), st), "ia_mc_count")

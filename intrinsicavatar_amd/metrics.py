@@ -97,7 +97,7 @@ def _mask(m: Optional[Tensor], n: int, what: str) -> Optional[Tensor]:
 
 
 def _tmp(dev) -> Tensor:
-    return torch.empty(int(L.lib().ia_metric_tmp_bytes()), dtype=torch.uint8, device=dev)
+    return L.work_area(L.lib().ia_metric_tmp_bytes(), dev)
 
 
 def squared_error(inputs: Tensor, targets: Tensor, valid_mask: Optional[Tensor] = None):
@@ -231,7 +231,7 @@ def ssim(inputs: Tensor, targets: Tensor, rect: Optional[Tensor] = None) -> Metr
             raise ValueError("SSIM: rect must be 4 int32 values on the device (mask_rect's output)")
         rect = rect.contiguous()
     lib, dev = L.lib(), a.device
-    tmp = torch.empty(int(lib.ia_metric_ssim_tmp_bytes(L.i32(H), L.i32(W), L.i32(Cn))), dtype=torch.uint8, device=dev)
+    tmp = L.work_area(lib.ia_metric_ssim_tmp_bytes(L.i32(H), L.i32(W), L.i32(Cn)), dev)
     buf = torch.empty(2, dtype=torch.float64, device=dev)
     L.check(lib.ia_metric_ssim(L.i32(H), L.i32(W), L.i32(Cn), L.ptr(a), L.ptr(b), L.ptr(rect), L.ptr(tmp), L.ptr(buf), L.stream()), "ia_metric_ssim")
     return MetricValue.make(buf, 1, "SSIM")

@@ -130,7 +130,7 @@ def traverse_grids(
         if out is not None:
             return out
 
-    scratch = torch.empty(int(lib.ia_traverse_scratch_bytes(L.i64(n_rays))), dtype=torch.uint8, device=dev)
+    scratch = L.work_area(lib.ia_traverse_scratch_bytes(L.i64(n_rays)), dev)
     pcnt = torch.empty(n_rays, dtype=torch.int64, device=dev)          # n_edges | n_samples << 32
     pstart = torch.empty(n_rays, dtype=torch.int64, device=dev)
     total = torch.empty(1, dtype=torch.int64, device=dev)               # written by the scan
@@ -181,7 +181,7 @@ def _traverse_fused(args, n_rays, aabb, step_size, max_extent, dev, incoherent=F
     if cap_e >= (1 << 31):
         return None
     lib, st = L.lib(), L.stream()
-    scratch = torch.empty(int(lib.ia_traverse_fused_scratch_bytes(L.i64(n_rays))), dtype=torch.uint8, device=dev)
+    scratch = L.work_area(lib.ia_traverse_fused_scratch_bytes(L.i64(n_rays)), dev)
     totals = torch.empty(3, dtype=torch.int64, device=dev)
     iv_vals = torch.empty(cap_e, dtype=torch.float32, device=dev)
     iv_flags = torch.empty((2, cap_e), dtype=torch.bool, device=dev)

@@ -21,7 +21,7 @@ def binarize(occs: Tensor, resolution, thre_max: float, keep_largest_component: 
     dev = occs.device
     binaries = torch.empty((rx, ry, rz), dtype=torch.bool, device=dev)
     thre = torch.empty(1, device=dev)
-    tmp = torch.empty(int(L.lib().ia_occgrid_tmp_bytes(L.i32(rx), L.i32(ry), L.i32(rz))), dtype=torch.uint8, device=dev)
+    tmp = L.work_area(L.lib().ia_occgrid_tmp_bytes(L.i32(rx), L.i32(ry), L.i32(rz)), dev)
     L.check(L.lib().ia_occgrid_binarize(L.i32(rx), L.i32(ry), L.i32(rz), L.ptr(occs), L.f32(thre_max),
                                         L.i32(int(keep_largest_component)), L.ptr(binaries), L.ptr(thre), L.ptr(tmp), L.stream()),
             "ia_occgrid_binarize")

@@ -105,7 +105,7 @@ class EnvironmentLightTensor(torch.nn.Module):
         if H * W <= self.PDF_KERNEL_MAX_PIXELS:
             self.pmf = torch.empty((H, W), device=base.device)
             self._cdf = torch.empty(H * W, dtype=torch.float64, device=base.device)
-            tmp = torch.empty(int(L.lib().ia_envlight_pdf_tables_tmp_bytes(L.i32(H), L.i32(W))), dtype=torch.uint8, device=base.device)
+            tmp = L.work_area(L.lib().ia_envlight_pdf_tables_tmp_bytes(L.i32(H), L.i32(W)), base.device)
             L.check(L.lib().ia_envlight_pdf_tables(L.i32(H), L.i32(W), L.ptr(base), L.ptr(self.pmf), L.ptr(self._cdf), L.ptr(tmp), L.stream()),
                     "ia_envlight_pdf_tables")
         else:        # larger than the kernel's tile table: the torch expression
@@ -167,7 +167,7 @@ class _SGImage(torch.autograd.Function):
         axis, log_lambda, mu = ctx.saved_tensors
         K = axis.shape[0]
         H, W = ctx.hw
-        tmp = torch.empty(int(L.lib().ia_sg_image_bwd_tmp_bytes(L.i32(K))), dtype=torch.uint8, device=axis.device)
+        tmp = L.work_area(L.lib().ia_sg_image_bwd_tmp_bytes(L.i32(K)), axis.device)
         g_axis, g_ll, g_mu = torch.empty_like(axis), torch.empty_like(log_lambda), torch.empty_like(mu)
         L.check(L.lib().ia_sg_image_bwd(L.i32(K), L.i32(H), L.i32(W), L.ptr(axis), L.ptr(log_lambda), L.ptr(mu), L.ptr(g_img.contiguous().float()),
                                         L.ptr(tmp), L.ptr(g_axis), L.ptr(g_ll), L.ptr(g_mu), L.stream()), "ia_sg_image_bwd")
@@ -343,7 +343,7 @@ class _PbrShade(torch.autograd.Function):
         g_base = L.zeros_like(env_base) if ctx.needs_input_grad[5] else None
         H, W, _ = env_base.shape
         nb = int(L.lib().ia_pbr_shade_bwd_scratch_bytes(L.i64(F_))) if g_base is not None else 0
-        scratch = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None
+        scratch = L.work_area(nb, dev) if nb else None
         L.check(L.lib().ia_pbr_shade_bwd(
             L.i32(ctx.mode), L.i64(F_), L.ptr(normal), L.ptr(albedo), L.ptr(roughness), L.ptr(metallic), L.ptr(view_dirs),
             L.ptr(out_dirs), L.ptr(tr), L.ptr(ind), L.ptr(inv_pdf), L.ptr(env_base), L.ptr(env_pmf), L.i32(H), L.i32(W),

@@ -119,7 +119,7 @@ class _PhysLoss(Function):
         terms = torch.empty(5, device=dev)
         k = int(eik_part.shape[0]) if eik_part is not None else 0
         nb = int(L.lib().ia_phys_loss_tmp_bytes(L.i64(n)))
-        tmp = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None
+        tmp = L.work_area(nb, dev) if nb else None
         L.check(L.lib().ia_phys_loss(L.i64(n), L.ptr(comp_rgb), L.ptr(comp_rgb_phys), L.ptr(opacity), L.ptr(target_rgb), L.ptr(target_mask),
                                      L.ptr(eik_part), L.i32(k), L.f32(lambda_phys), L.f32(lambda_mask), L.f32(lambda_eik), L.f32(eik_denom),
                                      L.ptr(terms), L.ptr(tmp), L.stream()), "ia_phys_loss")
