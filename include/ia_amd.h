@@ -849,6 +849,32 @@ int ia_sample_batch(int64_t n, int64_t num_mask, int64_t num_edge, int64_t frame
                     const int32_t* edge_loc, const double* cam_host, const float* near_tab, const float* far_tab, int64_t* indices,
                     float* alpha, float* rgb, float* rays_o, float* rays_d, float* near, float* far, int32_t* status, ia_stream_t stream);
 
+/* ------------------------------------------------------------------------- */
+/* Forward skinning and mesh attributes (csrc/lbs_fwd.hip, csrc/mesh_attr.hip): ForwardDeformer.forward_skinning
+ * (models/deformers/fast_snarf/deformer_torch.py:127-137 with query_weights :199-210 and skinning_mask :213-227) and the area-weighted
+ * vertex normals of a triangle mesh.  Conventions (corner order, summation orders): csrc/lbs_math.h and DESIGN.md "Forward skinning and
+ * mesh attributes".  None of the four needs a work area of its own; the caller allocates the typed lists.
+ *
+ * ia_forward_skinning: xc [P,3], grid [24,D,H,W], offset / scale [3], tfs [24,4,4] (all fp32, on the device) -> w [P,24] = grid_sample(
+ *   align_corners, bilinear, border) of the grid at (xc + offset) * scale (x -> W, y -> H, z -> D), xd [P,3] = T[:3,:3] xc + T[:3,3] with
+ *   T = sum_j w_j tfs_j in ascending j, R [P,3,3] = T[:3,:3].  Each output may be NULL; tfs may be NULL when xd and R are.  A point's
+ *   result does not depend on P or on the launch.
+ * ia_mesh_vertex_faces_count: faces [T,3] int64 -> counts [V+1] int32 = the number of face corners at each vertex (counts[V] = 0); the
+ *   exclusive scan of counts over V + 1 entries (ia_exclusive_scan_i32, in place) is `offsets`.  A face with an index outside [0, V) is
+ *   ignored here and below.  V < 2^31 - 1, 3 T < 2^31.
+ * ia_mesh_vertex_faces_fill: lists [3T] int32: lists[offsets[v] .. offsets[v+1]) = the faces at vertex v, in no particular order;
+ *   cursor [V] int32 is overwritten.
+ * ia_mesh_vertex_normals: sorts every vertex's list in place (ascending face index), then v_nrm [V,3] = n / max(|n|, 1e-12) with n =
+ *   the sum over the list, in that order, of (v1 - v0) x (v2 - v0) of v_pos [V,3].  No float atomics: lists and normals do not depend on
+ *   scheduling. */
+int ia_forward_skinning(int64_t P, const float* xc, const float* grid, int D, int H, int W, const float* offset, const float* scale,
+                        const float* tfs, float* w, float* xd, float* R, ia_stream_t stream);
+int ia_mesh_vertex_faces_count(int64_t T, int64_t V, const int64_t* faces, int32_t* counts, ia_stream_t stream);
+int ia_mesh_vertex_faces_fill(int64_t T, int64_t V, const int64_t* faces, const int32_t* offsets, int32_t* cursor, int32_t* lists,
+                              ia_stream_t stream);
+int ia_mesh_vertex_normals(int64_t V, int64_t T, const float* v_pos, const int64_t* faces, const int32_t* offsets, int32_t* lists,
+                           float* v_nrm, ia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,8 @@ SOURCES = {
     "metrics.hip": ["-ffp-contract=off"],
     "skinning.hip": ["-ffp-contract=off"],
     "data.hip": ["-ffp-contract=off"],
+    "lbs_fwd.hip": ["-ffp-contract=off"],
+    "mesh_attr.hip": ["-ffp-contract=off"],
 }
 
 

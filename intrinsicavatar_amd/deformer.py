@@ -173,13 +173,28 @@ class SNARFDeformer:
             return x[0], valid[0], (fwd[0] if want_fwd else None), Jinv[0]
         return x[0], valid[0], (fwd[0] if want_fwd else None)
 
+    def _lbs(self, xc: Tensor, want_weights: bool, want_xd: bool, want_rot: bool):
+        """fast_snarf.forward_skinning on this deformer's grid and prepared pose -> (xd, R, w), None where not asked for.  The weights
+        alone need no pose."""
+        tfs = None
+        if want_xd or want_rot:
+            if self.tfs is None:
+                raise RuntimeError("SNARFDeformer.forward_skinning: no pose (call prepare(tfs, w2s) first)")
+            tfs = self.tfs[:1]
+        return fast_snarf.forward_skinning(xc, self.lbs_voxel_final, tfs, self.offset_kernel, self.scale_kernel,
+                                           want_weights=want_weights, want_xd=want_xd, want_rot=want_rot)
+
+    def forward_skinning(self, xc: Tensor, want_weights: bool = False, want_rot: bool = True):
+        """ForwardDeformer.forward_skinning (deformer_torch.py:127-137) of canonical points xc [P,3] with the prepared pose: (xd [P,3],
+        R [P,3,3]) = (the skinned points, the blended T[:, :3, :3] -- the reference's two return values; R is None without want_rot),
+        followed by the weights [P,24] when want_weights.  One kernel (ia_forward_skinning); values only, no autograd graph."""
+        xd, R, w = self._lbs(xc, want_weights, True, want_rot)
+        return (xd, R, w) if want_weights else (xd, R)
+
     def query_weights(self, xc: Tensor) -> Tensor:
         """skinning weights [P,24] at canonical points: trilinear, align_corners, border-clamped lookup of lbs_voxel_final
-        (deformer_torch.py:198-209)."""
-        g = ((xc + self.offset_kernel) * self.scale_kernel).reshape(1, -1, 1, 1, 3)
-        w = torch.nn.functional.grid_sample(self.lbs_voxel_final, g, align_corners=True, mode="bilinear",
-                                            padding_mode="border")
-        return w.reshape(w.shape[1], -1).t()
+        (deformer_torch.py:198-209) by the forward-skinning kernel."""
+        return self._lbs(xc, True, False, False)[2]
 
     def implicit_pose_terms(self, xc: Tensor, J_inv: Tensor, valid: Tensor):
         """the two places the bone transforms enter the training graph (ForwardDeformer.forward, version 1,
@@ -187,9 +202,9 @@ class SNARFDeformer:
           * xc + correction, correction = -J_inv (LBS(xc, tfs) - stopgrad(LBS(xc, tfs))): zero in value, and its derivative
             with respect to tfs is the implicit-function derivative of the root;
           * the linearly blended rotation block T[:, :3, :3] that pushes normals to observation space.
-        xc, J_inv, valid are constants (no_grad search results); self.tfs carries the graph."""
-        with torch.no_grad():
-            w = self.query_weights(xc)                                          # [P,24]
+        xc, J_inv, valid are constants (no_grad search results); self.tfs carries the graph: the weights come from the forward-skinning
+        kernel, and the blend, linear in tfs given the weights, stays a torch expression so that autograd sees it."""
+        w = self.query_weights(xc)                                              # [P,24]
         T = (w @ self.tfs[0].reshape(w.shape[1], 16)).reshape(-1, 4, 4)
         R = T[:, :3, :3]
         xd = (R * xc[:, None, :]).sum(-1) + T[:, :3, 3]

@@ -5,7 +5,8 @@ models/deformers/fast_snarf/deformer_torch.py:9-18:
     filter_cuda.filter(...)         -> filter.cu:10-77
     precompute_cuda.precompute(...) -> precompute.cu:24-103
 
-Same positional signatures (in-place outputs, None return for fuse_broyden / precompute).
+Same positional signatures (in-place outputs, None return for fuse_broyden / precompute).  `forward_skinning` is the deformer's own
+forward_skinning (deformer_torch.py:127-137, torch code in the reference) as one kernel.
 `ChannelLastVoxelJ` is the MI355X-native extension: the channel-last copy of voxel_J that
 `precompute` can emit for free and `fuse_broyden` gathers 4x more efficiently.
 """
@@ -169,6 +170,37 @@ def filter(x: Tensor, mask: Tensor) -> Tensor:
     out = torch.empty_like(mask)
     L.check(L.lib().ia_filter(L.i64(N), L.i32(I), L.ptr(x), L.ptr(mask), L.ptr(out), L.stream()), "ia_filter")
     return out
+
+
+@torch.no_grad()
+def forward_skinning(xc: Tensor, voxel_w: Tensor, tfs: Tensor, offset: Tensor, scale: Tensor, want_weights: bool = False,
+                     want_xd: bool = True, want_rot: bool = True):
+    """ForwardDeformer.forward_skinning (deformer_torch.py:127-137: query_weights :199-210 + skinning_mask :213-227) as one kernel
+    (ia_forward_skinning, csrc/lbs_fwd.hip): xc [..., 3] canonical points, voxel_w [1,24,D,H,W] the skinning-weight grid, tfs [1,24,4,4]
+    (or [24,4,4]; None when only the weights are wanted), offset / scale the grid's offset_kernel / scale_kernel ->
+    (xd [P,3], R [P,3,3] = the blended T[:, :3, :3], w [P,24]); an output that is not wanted is None.  Values only (no autograd graph)."""
+    if not xc.is_cuda:
+        raise L.IaError("forward_skinning needs GPU tensors (no CPU fallback)")
+    if voxel_w.dim() != 5 or voxel_w.shape[0] != 1 or voxel_w.shape[1] != 24:
+        raise RuntimeError("forward_skinning: voxel_w must be [1,24,D,H,W]")
+    _, _, D, H, W = voxel_w.shape
+    dev = xc.device
+    xc = xc.detach().reshape(-1, 3).contiguous().float()
+    P = xc.shape[0]
+    if want_xd or want_rot:
+        if tfs is None or tfs.numel() != 24 * 16:
+            raise RuntimeError("forward_skinning: xd and R need tfs [1,24,4,4]")
+        tfs = tfs.detach().reshape(24, 4, 4).contiguous().float()
+    else:
+        tfs = None
+    w = torch.empty((P, 24), dtype=torch.float32, device=dev) if want_weights else None
+    xd = torch.empty((P, 3), dtype=torch.float32, device=dev) if want_xd else None
+    R = torch.empty((P, 3, 3), dtype=torch.float32, device=dev) if want_rot else None
+    L.check(L.lib().ia_forward_skinning(L.i64(P), L.ptr(xc), L.ptr(voxel_w.detach().contiguous().float()), L.i32(D), L.i32(H), L.i32(W),
+                                        L.ptr(offset.detach().reshape(3).contiguous().float()),
+                                        L.ptr(scale.detach().reshape(3).contiguous().float()), L.ptr(tfs), L.ptr(w), L.ptr(xd), L.ptr(R),
+                                        L.stream()), "ia_forward_skinning")
+    return xd, R, w
 
 
 # -- building the skinning-weight grid from a body surface (deformer_torch.py:139-253; csrc/skinning.hip) --------------------------

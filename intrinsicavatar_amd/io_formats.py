@@ -6,7 +6,8 @@
     rgb_image_u8 / grayscale_image_u8 / image_grid_u8 / save_image_grid
                                  the panels the reference's SaverMixin writes per validation / test image
                                  (utils/mixins.py:43-58, 87-122, 124-155), as RGB uint8 arrays / PNG files via PIL
-    save_obj / load_obj          the exported mesh (SaverMixin.save_mesh's `.obj`) as plain `v` / `f` lines, without trimesh
+    save_obj / load_obj          the exported mesh (SaverMixin.save_mesh's `.obj`) as plain `v` / `f` (optionally `vn`) lines, without trimesh
+    save_skinned_npz             the animatable mesh: vertices, faces, normals, [V,24] skinning weights
 
 `.exr` needs OpenEXR, which this image does not have: load_hdri raises for it.  Checkpoint key layout and SMPL kinematics are
 covered in checkpoint-facing modules (fields.py, smpl.py)."""
@@ -175,23 +176,37 @@ def save_image_grid(path: str, imgs: Sequence) -> np.ndarray:
 
 
 # ----------------------------------------------------------------------------- Wavefront OBJ (the exported mesh)
-def save_obj(path: str, v_pos, t_pos_idx) -> None:
+def save_obj(path: str, v_pos, t_pos_idx, v_nrm=None) -> None:
     """SaverMixin.save_mesh's `.obj` without trimesh: one `v x y z` line per vertex (%.9g: float32 values round-trip exactly) and one
-    `f a b c` line per face with 1-based indices, in the given order (no vertex merging, no normals, no colour)."""
+    `f a b c` line per face with 1-based indices, in the given order (no vertex merging, no colour).  With v_nrm [V,3]: one `vn x y z`
+    line per vertex after the `v` lines, and faces as `f a//a b//b c//c` (a vertex and its normal share an index); without it the file
+    is what it always was."""
     v = np.ascontiguousarray(_np(v_pos), dtype=np.float32).reshape(-1, 3)
     f = np.ascontiguousarray(_np(t_pos_idx), dtype=np.int64).reshape(-1, 3)
+    n = None
+    if v_nrm is not None:
+        n = np.ascontiguousarray(_np(v_nrm), dtype=np.float32).reshape(-1, 3)
+        if n.shape != v.shape:
+            raise ValueError(f"save_obj: v_nrm {n.shape} does not match v_pos {v.shape}")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as fh:
         if len(v):
             np.savetxt(fh, v.astype(np.float64), fmt="v %.9g %.9g %.9g")
+        if n is not None and len(n):
+            np.savetxt(fh, n.astype(np.float64), fmt="vn %.9g %.9g %.9g")
         if len(f):
-            np.savetxt(fh, f + 1, fmt="f %d %d %d")
+            if n is None:
+                np.savetxt(fh, f + 1, fmt="f %d %d %d")
+            else:
+                np.savetxt(fh, np.repeat(f + 1, 2, axis=1), fmt="f %d//%d %d//%d %d//%d")
 
 
-def load_obj(path: str):
+def load_obj(path: str, with_normals: bool = False):
     """(v_pos float32 [V,3], t_pos_idx int64 [T,3] 0-based) of the `v` and triangular `f` lines of an `.obj` (as save_obj writes them;
-    `f a/b/c` index forms keep the position index)."""
+    `f a/b/c` index forms keep the position index).  with_normals: a third array, the `vn` lines as float32 [N,3]; a face corner
+    `a//n` must then name the same index twice (save_obj's layout: one normal per vertex)."""
     vs: List[List[float]] = []
+    ns: List[List[float]] = []
     fs: List[List[int]] = []
     with open(path) as fh:
         for line in fh:
@@ -200,8 +215,34 @@ def load_obj(path: str):
                 continue
             if tok[0] == "v":
                 vs.append([float(t) for t in tok[1:4]])
+            elif tok[0] == "vn":
+                ns.append([float(t) for t in tok[1:4]])
             elif tok[0] == "f":
                 if len(tok) != 4:
                     raise ValueError(f"{path}: only triangular faces are supported")
-                fs.append([int(t.split("/")[0]) - 1 for t in tok[1:4]])
-    return np.array(vs, dtype=np.float32).reshape(-1, 3), np.array(fs, dtype=np.int64).reshape(-1, 3)
+                parts = [t.split("/") for t in tok[1:4]]
+                if with_normals and any(len(q) == 3 and q[2] and q[2] != q[0] for q in parts):
+                    raise ValueError(f"{path}: a face corner's normal index differs from its vertex index")
+                fs.append([int(q[0]) - 1 for q in parts])
+    out = (np.array(vs, dtype=np.float32).reshape(-1, 3), np.array(fs, dtype=np.int64).reshape(-1, 3))
+    return out + (np.array(ns, dtype=np.float32).reshape(-1, 3),) if with_normals else out
+
+
+def save_skinned_npz(path: str, mesh, weights, tfs=None) -> None:
+    """the animatable form of an exported mesh as one `.npz`: v_pos float32 [V,3], t_pos_idx int64 [T,3], v_nrm float32 [V,3] (the mesh
+    dict of mesh.pose / mesh.isosurface + mesh.vertex_normals), weights float32 [V,24] (mesh.skinning_weights), and, when given, tfs
+    float32 [24,4,4]: the bone transforms the mesh was posed with (a canonical mesh carries none).  Linear blend skinning of v_pos with
+    `weights` and any other [24,4,4] transforms reproduces mesh.pose for that pose."""
+    v = np.ascontiguousarray(_np(mesh["v_pos"]), dtype=np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(_np(mesh["t_pos_idx"]), dtype=np.int64).reshape(-1, 3)
+    if "v_nrm" not in mesh:
+        raise ValueError("save_skinned_npz: the mesh has no 'v_nrm' (mesh.vertex_normals)")
+    n = np.ascontiguousarray(_np(mesh["v_nrm"]), dtype=np.float32).reshape(-1, 3)
+    w = np.ascontiguousarray(_np(weights), dtype=np.float32)
+    if n.shape != v.shape or w.shape != (v.shape[0], 24):
+        raise ValueError(f"save_skinned_npz: v_pos {v.shape}, v_nrm {n.shape}, weights {w.shape} do not belong to one mesh")
+    arrays = dict(v_pos=v, t_pos_idx=f, v_nrm=n, weights=w)
+    if tfs is not None:
+        arrays["tfs"] = np.ascontiguousarray(_np(tfs), dtype=np.float32).reshape(24, 4, 4)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.savez_compressed(path, **arrays)

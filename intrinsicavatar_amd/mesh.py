@@ -6,6 +6,9 @@ models/intrinsic_avatar.py:277-279 and 1685-1701, systems/intrinsic_avatar.py:92
                                                    BaseImplicitGeometry.isosurface: coarse pass over the geometry's bbox, fine pass
                                                    over the coarse mesh's extent grown by 10 % (clamped to the bbox)
     export(geometry, export_config)                IntrinsicAvatar.export: the mesh alone (the reference attaches no vertex colour)
+    vertex_normals(v_pos, t_pos_idx)               area-weighted vertex normals [V,3], bit-reproducible (csrc/mesh_attr.hip)
+    skinning_weights(mesh, deformer)               [V,24] skinning weights of the vertices (the deformer's grid, csrc/lbs_fwd.hip)
+    pose(mesh, deformer)                           the mesh skinned with the deformer's prepared pose + its normals there
 
 The grid points, the SDF (VolumeSDF.sdf_only, chunk by chunk) and the extraction (csrc/mcubes.hip) stay on the device; a marching-cubes
 call reads back its two output sizes once, isosurface() additionally the coarse mesh's extent (6 floats).  Conventions of the
@@ -13,6 +16,9 @@ extraction: csrc/mc_math.h and DESIGN.md "Mesh export".
 
     python -m intrinsicavatar_amd.mesh --state-dict CKPT --bbox x0 y0 z0 x1 y1 z1 [--resolution 512] [--global-step 25000] --out mesh.obj
     python -m intrinsicavatar_amd.mesh --state-dict CKPT --smpl-npz BODY.npz [--cano-pose A_pose] ... --out mesh.obj
+    ... --normals                                  `vn` lines in the .obj
+    ... --smpl-npz BODY.npz --pose-npz POSES.npz --frame K [--skinned-npz OUT.npz]
+                                                   the mesh posed for frame K of POSES.npz (body_pose [F,69], global_orient [F,3], transl [F,3])
 """
 import argparse
 import ctypes as C
@@ -128,20 +134,108 @@ def export(geometry, export_config=None) -> Dict[str, torch.Tensor]:
     return geometry.isosurface()
 
 
-def smpl_npz_bbox(path: str, cano_pose="A_pose") -> torch.Tensor:
-    """[2,3] float32 canonical bbox of the body stored in an .npz (the arrays smpl.SMPLKinematics takes, plus betas): the body in its
-    canonical pose, then smpl.bbox_from_vertices (SNARFDeformer.initialize, snarf_deformer.py:46-71).  24 joints on the host."""
+def vertex_faces(n_vertices: int, t_pos_idx: torch.Tensor):
+    """the vertex -> incident-faces lists of a triangle mesh as CSR: (offsets int32 [V+1], lists int32 [3T]); lists[offsets[v] ..
+    offsets[v+1]) holds the faces at vertex v in no particular order (vertex_normals sorts them).  Integer atomics + the library's
+    exclusive scan; a face with an index outside [0, V) is in no list."""
+    if not t_pos_idx.is_cuda:
+        raise L.IaError("mesh.vertex_faces needs GPU tensors (no CPU fallback)")
+    faces = t_pos_idx.reshape(-1, 3).contiguous().to(torch.int64)
+    V, T = int(n_vertices), int(faces.shape[0])
+    lib, st, dev = L.lib(), L.stream(), faces.device
+    offsets = torch.empty(V + 1, dtype=torch.int32, device=dev)
+    L.check(lib.ia_mesh_vertex_faces_count(L.i64(T), L.i64(V), L.ptr(faces), L.ptr(offsets), st), "ia_mesh_vertex_faces_count")
+    L.check(lib.ia_exclusive_scan_i32(L.ptr(offsets), L.ptr(offsets), L.ptr(None), L.i64(V + 1), L.ptr(L.scan_tmp(V + 1, dev)), st),
+            "ia_exclusive_scan_i32")
+    cursor = torch.empty(max(V, 1), dtype=torch.int32, device=dev)
+    lists = torch.empty(max(3 * T, 1), dtype=torch.int32, device=dev)
+    L.check(lib.ia_mesh_vertex_faces_fill(L.i64(T), L.i64(V), L.ptr(faces), L.ptr(offsets), L.ptr(cursor), L.ptr(lists), st),
+            "ia_mesh_vertex_faces_fill")
+    return offsets, lists[:3 * T]
+
+
+@torch.no_grad()
+def vertex_normals(v_pos: torch.Tensor, t_pos_idx: torch.Tensor, return_lists: bool = False):
+    """area-weighted vertex normals [V,3] fp32 of the mesh v_pos [V,3], t_pos_idx [T,3]: the sum of the un-normalised
+    (v1 - v0) x (v2 - v0) over the faces at the vertex, in ascending face index, then n / max(|n|, 1e-12).  No float atomics: two runs,
+    and runs on differently scheduled devices, give the same bits (csrc/mesh_attr.hip, csrc/lbs_math.h).  A vertex of no face gets 0.
+    return_lists: (v_nrm, offsets int32 [V+1], lists int32 [3T]) with every vertex's list sorted."""
+    if not v_pos.is_cuda:
+        raise L.IaError("mesh.vertex_normals needs GPU tensors (no CPU fallback)")
+    if v_pos.dim() != 2 or v_pos.shape[1] != 3 or t_pos_idx.dim() != 2 or t_pos_idx.shape[1] != 3:
+        raise ValueError(f"vertex_normals needs v_pos [V,3] and t_pos_idx [T,3], got {tuple(v_pos.shape)} and {tuple(t_pos_idx.shape)}")
+    v = v_pos.detach().contiguous().float()
+    faces = t_pos_idx.contiguous().to(torch.int64)
+    V, T = int(v.shape[0]), int(faces.shape[0])
+    offsets, lists = vertex_faces(V, faces)
+    v_nrm = torch.empty((V, 3), dtype=torch.float32, device=v.device)
+    L.check(L.lib().ia_mesh_vertex_normals(L.i64(V), L.i64(T), L.ptr(v), L.ptr(faces), L.ptr(offsets), L.ptr(lists), L.ptr(v_nrm),
+                                           L.stream()), "ia_mesh_vertex_normals")
+    return (v_nrm, offsets, lists) if return_lists else v_nrm
+
+
+@torch.no_grad()
+def skinning_weights(mesh: Dict[str, torch.Tensor], deformer) -> torch.Tensor:
+    """[V,24] skinning weights of the mesh's vertices: the deformer's weight grid at v_pos (SNARFDeformer.query_weights)."""
+    return deformer.query_weights(mesh["v_pos"])
+
+
+@torch.no_grad()
+def pose(mesh: Dict[str, torch.Tensor], deformer) -> Dict[str, torch.Tensor]:
+    """the canonical mesh in the deformer's prepared pose (deformer.prepare(tfs, w2s)): v_pos skinned forward with deformer.tfs
+    (SNARFDeformer.forward_skinning; SMPL-root frame, as tfs is), the faces shared with `mesh` (not copied), and v_nrm = the vertex
+    normals of the posed surface (vertex_normals of the posed vertices)."""
+    xd, _ = deformer.forward_skinning(mesh["v_pos"], want_rot=False)
+    return {"v_pos": xd, "t_pos_idx": mesh["t_pos_idx"], "v_nrm": vertex_normals(xd, mesh["t_pos_idx"])}
+
+
+def _smpl_npz_body(path: str, device="cpu", dtype=torch.float64):
+    """(smpl.SMPLKinematics, betas [1,NB]) of the body stored in an .npz (the arrays SMPLKinematics takes, plus betas)."""
     import numpy as np
     from . import smpl
     z = np.load(path)
     missing = [k for k in ("v_template", "shapedirs", "posedirs", "J_regressor", "parents", "lbs_weights", "betas") if k not in z.files]
     if missing:
         raise SystemExit(f"{path}: missing arrays {missing}")
-    t = lambda k: torch.from_numpy(np.asarray(z[k], dtype=np.float64))      # noqa: E731
+    t = lambda k: torch.from_numpy(np.asarray(z[k], dtype=np.float64)).to(device=device, dtype=dtype)      # noqa: E731
     body = smpl.SMPLKinematics(t("v_template"), t("shapedirs"), t("posedirs"), t("J_regressor"), z["parents"].tolist(), t("lbs_weights"))
+    return body, t("betas").reshape(-1, body.shapedirs.shape[-1])[:1]
+
+
+def _cano_pose_arg(cano_pose):
     if isinstance(cano_pose, str) and "," in cano_pose:
-        cano_pose = [float(v) for v in cano_pose.split(",")]
-    betas = t("betas").reshape(-1, body.shapedirs.shape[-1])[:1]
+        return [float(v) for v in cano_pose.split(",")]
+    return cano_pose
+
+
+def smpl_npz_deformer(smpl_npz: str, pose_npz: str, frame: int, cano_pose="A_pose", device="cuda:0", resolution: int = 128):
+    """the deformer of the body in `smpl_npz`, prepared for frame `frame` of `pose_npz` (body_pose [F,69], global_orient [F,3],
+    transl [F,3]): deformer.initialize, then smpl.SMPLKinematics.forward + smpl.deformer_transforms + deformer.prepare
+    (SNARFDeformer.initialize / prepare_deformer, snarf_deformer.py:46-126).  -> (deformer, tfs [1,24,4,4])"""
+    import numpy as np
+    from . import deformer as D, smpl
+    body, betas = _smpl_npz_body(smpl_npz, device=device, dtype=torch.float32)
+    z = np.load(pose_npz)
+    missing = [k for k in ("body_pose", "global_orient", "transl") if k not in z.files]
+    if missing:
+        raise SystemExit(f"{pose_npz}: missing arrays {missing}")
+    F = z["body_pose"].shape[0]
+    if not 0 <= frame < F:
+        raise SystemExit(f"{pose_npz}: --frame {frame} outside 0 .. {F - 1}")
+    t = lambda k: torch.from_numpy(np.asarray(z[k][frame:frame + 1], dtype=np.float32)).reshape(1, -1).to(device)      # noqa: E731
+    dfm, A_rest_inv, _, _ = D.initialize(body, betas, _cano_pose_arg(cano_pose), resolution=resolution)
+    out = body.forward(betas, t("body_pose"), t("global_orient"), t("transl"))
+    tfs, w2s = smpl.deformer_transforms(out["A"], A_rest_inv)
+    dfm.prepare(tfs, w2s[0])
+    return dfm, tfs
+
+
+def smpl_npz_bbox(path: str, cano_pose="A_pose") -> torch.Tensor:
+    """[2,3] float32 canonical bbox of the body stored in an .npz (the arrays smpl.SMPLKinematics takes, plus betas): the body in its
+    canonical pose, then smpl.bbox_from_vertices (SNARFDeformer.initialize, snarf_deformer.py:46-71).  24 joints on the host."""
+    from . import smpl
+    body, betas = _smpl_npz_body(path)
+    cano_pose = _cano_pose_arg(cano_pose)
     out = body.forward(betas, smpl.rest_pose(cano_pose).double(), torch.zeros((1, 3), dtype=torch.float64))
     return smpl.bbox_from_vertices(out["vertices"].float())
 
@@ -163,7 +257,17 @@ def main(argv=None) -> int:
     ap.add_argument("--prefix", default="model.")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--out", required=True)
+    ap.add_argument("--normals", action="store_true", help="write area-weighted vertex normals (`vn` lines, `f a//a b//b c//c`)")
+    ap.add_argument("--pose-npz", metavar="FILE", help="pose the mesh: body_pose [F,69], global_orient [F,3], transl [F,3]; the body "
+                    "comes from --smpl-npz, its bone transforms through smpl.SMPLKinematics + smpl.deformer_transforms")
+    ap.add_argument("--frame", type=int, default=0, help="frame of --pose-npz")
+    ap.add_argument("--skinned-npz", metavar="FILE", help="also write the animatable form (vertices, faces, normals, [V,24] skinning "
+                    "weights, the frame's bone transforms): needs --pose-npz")
     a = ap.parse_args(argv)
+    if a.pose_npz is not None and a.smpl_npz is None:
+        ap.error("--pose-npz needs the body of --smpl-npz")
+    if a.skinned_npz is not None and a.pose_npz is None:
+        ap.error("--skinned-npz needs --pose-npz")
     from . import checkpoint, fields, io_formats
     ck = torch.load(a.state_dict, map_location="cpu", weights_only=False)       # a Lightning file also pickles its hyper-parameters
     sd = ck.get("state_dict", ck)
@@ -177,7 +281,15 @@ def main(argv=None) -> int:
     geo.prepare_bbox(bbox.to(a.device))
     geo.update_step(0, a.global_step)
     mesh = isosurface(geo, a.resolution, a.chunk, a.threshold)
-    io_formats.save_obj(a.out, mesh["v_pos"], mesh["t_pos_idx"])
+    if a.pose_npz is not None:
+        dfm, tfs = smpl_npz_deformer(a.smpl_npz, a.pose_npz, a.frame, a.cano_pose, a.device)
+        if a.skinned_npz is not None:
+            cano = dict(mesh, v_nrm=vertex_normals(mesh["v_pos"], mesh["t_pos_idx"]))
+            io_formats.save_skinned_npz(a.skinned_npz, cano, skinning_weights(mesh, dfm), tfs[0])
+        mesh = pose(mesh, dfm)
+    elif a.normals:
+        mesh["v_nrm"] = vertex_normals(mesh["v_pos"], mesh["t_pos_idx"])
+    io_formats.save_obj(a.out, mesh["v_pos"], mesh["t_pos_idx"], mesh["v_nrm"] if a.normals else None)
     print(f"{a.out}: {mesh['v_pos'].shape[0]} vertices, {mesh['t_pos_idx'].shape[0]} faces")
     return 0
 
