@@ -515,9 +515,11 @@ __global__ __launch_bounds__(THREADS) void shade_prep_bwd_kernel(int64_t n, cons
     // normal_smpl = g / max(|g|, 1e-6) (the BRDF's normal in the PBR branch): its gradient joins here instead of in five torch launches
     float gs[3] = {0.f, 0.f, 0.f};
     if (g_ns) {
-        const float nrm = fmaxf(sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]), 1e-6f);
+        const float glen = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+        const float nrm = fmaxf(glen, 1e-6f);
         const float ns[3] = {g[0] / nrm, g[1] / nrm, g[2] / nrm};
-        const float dsn = g_ns[i * 3 + 0] * ns[0] + g_ns[i * 3 + 1] * ns[1] + g_ns[i * 3 + 2] * ns[2];
+        // below the clamp the denominator is the constant 1e-6: no projection term (as for normal_world above)
+        const float dsn = glen > 1e-6f ? g_ns[i * 3 + 0] * ns[0] + g_ns[i * 3 + 1] * ns[1] + g_ns[i * 3 + 2] * ns[2] : 0.0f;
 #pragma unroll
         for (int c = 0; c < 3; c++) gs[c] = (g_ns[i * 3 + c] - dsn * ns[c]) / nrm;
     }

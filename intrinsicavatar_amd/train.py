@@ -197,7 +197,7 @@ class _Eikonal(Function):
 class _EikonalPartials(Function):
     """sdf_grad [n,3], valid [n] -> the per-workgroup partial sums [k,2] of ia_eikonal as they are (column 0: sum over valid of
     (|g| - 1)^2): train_phys._PhysLoss adds them up inside its own kernel.  The gradient that comes back is the SAME scalar for every
-    partial (d loss / d sum), read from the first element."""
+    partial (d loss / d sum), read from the first element.  n = 0 has no workgroup: ONE all-zero row is returned then."""
 
     @staticmethod
     def forward(ctx, sdf_grad, valid):

@@ -156,7 +156,8 @@ def test_pose_gradients_vs_torch_autograd(frame):
 
 def test_fused_mlp_backward_matches_operand_path():
     """csrc/mlp_train.hip (operands in LDS, dW in MFMA accumulators) == csrc/mlp_bwd.hip + ia_wgrad (operands through
-    HBM) for the radiance head and the SDF head incl. its second-order terms; ragged n (not a multiple of 32)."""
+    HBM) for the radiance head and the SDF head incl. its second-order terms; ragged n (not a multiple of 32).
+    Each path against fp64 autograd, all kinds and sizes: tests/test_gpu_backward_kernels.py."""
     import ctypes as C
     from intrinsicavatar_amd import build
     build.build()
