@@ -524,6 +524,18 @@ int ia_brdf_pdf(int64_t F, const float* normal, const float* view_dirs, const fl
 /* emitter.eval / emitter.pdf on world-space unit directions (either output may be NULL) */
 int ia_envlight_eval(int64_t n, const float* dirs_world, const float* env_base, const float* env_pmf, int env_h,
                      int env_w, float* rgb /*[n,3]*/, float* pdf /*[n]*/, ia_stream_t stream);
+/* add_emitter (models/intrinsic_avatar.py:1319-1333, :1455-1490): the emitter's radiance along camera rays.  Per ray
+ * d_world = normalize(rays_d_smpl @ w2s_rot) (transform_dirs_s2w: the matrix itself, |x| clamped at 1e-6), then the bilinear lookup of
+ * ia_envlight_eval.  ia_transform_dirs_s2w writes those world directions alone (the same device function). */
+int ia_transform_dirs_s2w(int64_t n, const float* dirs_smpl, const float* w2s_rot, float* dirs_world, ia_stream_t stream);
+int ia_envlight_background(int64_t n, const float* rays_d_smpl, const float* w2s_rot, const float* env_base, int env_h, int env_w,
+                           float* out /*[n,3]*/, ia_stream_t stream);
+/* d L / d env texels of the above: g_base [H,W,3] += bilinear scatter of g_out [n,3]; directions get no gradient.  The sums run in the
+ * 64-bit fixed point of ia_pbr_shade_bwd's texel path (scale 2^(62 - ceil(log2 n)) / max|g_out|), added with integer atomics: they do not
+ * depend on the order, the gradient is bit-reproducible.  acc [H,W,3] int64 and gmax [1] uint32: the integer image and the bits of
+ * max|g_out|, caller-allocated with exactly these shapes, overwritten (the entry point clears them itself). */
+int ia_envlight_background_bwd(int64_t n, const float* rays_d_smpl, const float* w2s_rot, const float* g_out, int env_h, int env_w,
+                               float* g_base, int64_t* acc, uint32_t* gmax, ia_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
 /* Occupancy-grid maintenance (TemporalOccGridEstimator._update, models/occ_grid/temporal_occ_grid.py:369-411;
@@ -600,6 +612,10 @@ int ia_vi_composite_bwd(int64_t n_rays, int64_t F, const int32_t* resampled_pack
                         const int32_t* fg_ray, const float* weights_fg, const float* Lo, const float* background,
                         const float* background_rays /* as passed to the forward */, const float* g_rgb, float* g_weights_fg,
                         float* g_Lo, float* g_transmittance, ia_stream_t stream);
+/* gradient of the per-ray background (add_emitter): g_background_rays[r] = c_r * g_rgb[r] with c_r the factor ia_vi_composite multiplied
+ * background_rays[r] with: 1 on a ray without re-samples, transmittance[r] where bg_counts[r] > 0, 0 otherwise */
+int ia_vi_composite_bwd_bg(int64_t n_rays, const int32_t* resampled_packed_info, const int32_t* bg_counts, const float* transmittance,
+                           const float* g_rgb, float* g_background_rays /*[n,3]*/, ia_stream_t stream);
 /* the reference's index lists: fg_indices [F], bg_indices [R-F], resampled_ray_indices [R], resampled_weights [R] (each optional) */
 int ia_vi_indices(int64_t n_rays, int spp, const int32_t* resampled_packed_info, const int32_t* fg_ray_cnt,
                   const int32_t* fg_start, const int32_t* bg_counts, const int64_t* sampled_idx, const int32_t* fg_counts,

@@ -751,6 +751,78 @@ __global__ __launch_bounds__(THREADS) void env_eval_kernel(int64_t n, const floa
     if (pdf) pdf[i] = env_pdf(env, d);
 }
 
+// ---- add_emitter: the emitter's radiance along camera rays (models/intrinsic_avatar.py:1319-1333, :1455-1490) ---------------------------
+// transform_dirs_s2w (snarf_deformer.py:154-158): normalize(d @ w2s[:3,:3]) -- the matrix itself, not its transpose; |x| clamped at 1e-6
+__device__ __forceinline__ void dirs_s2w(const float d[3], const float* __restrict__ Rw, float dw[3])
+{
+    // every operation spelled out (no contraction left to the compiler): the kernels that share this function agree bit for bit
+#pragma unroll
+    for (int c = 0; c < 3; c++) dw[c] = __fmaf_rn(d[2], Rw[2 * 3 + c], __fmaf_rn(d[1], Rw[1 * 3 + c], __fmul_rn(d[0], Rw[0 * 3 + c])));
+    const float l = fmaxf(__fsqrt_rn(__fmaf_rn(dw[2], dw[2], __fmaf_rn(dw[1], dw[1], __fmul_rn(dw[0], dw[0])))), 1e-6f);
+    dw[0] = __fdiv_rn(dw[0], l); dw[1] = __fdiv_rn(dw[1], l); dw[2] = __fdiv_rn(dw[2], l);
+}
+
+// one lane per ray: 12 B in, 12 B out, 4 texels x 12 B from the cached map.  Either output may be NULL: `dirs_world` alone is
+// ia_transform_dirs_s2w -- the same kernel, so the directions it shows are the ones the lookup used
+__global__ __launch_bounds__(THREADS) void env_background_kernel(int64_t n, const float* __restrict__ rays_d, const float* __restrict__ Rw,
+                                                                  EnvMap env, float* __restrict__ out, float* __restrict__ dirs_world)
+{
+    const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= n) return;
+    const float d[3] = {rays_d[i * 3], rays_d[i * 3 + 1], rays_d[i * 3 + 2]};
+    float dw[3];
+    dirs_s2w(d, Rw, dw);
+    if (dirs_world) { dirs_world[i * 3] = dw[0]; dirs_world[i * 3 + 1] = dw[1]; dirs_world[i * 3 + 2] = dw[2]; }
+    if (out) {
+        float o[3];
+        env_eval(env, dw, o);
+        out[i * 3] = o[0]; out[i * 3 + 1] = o[1]; out[i * 3 + 2] = o[2];
+    }
+}
+
+// backward w.r.t. the texels, in the 64-bit fixed point of the band path above (env_fixed_scale / env_fixed_finish_kernel): max |g| first,
+// then every ray adds round(w g S) to the caller's integer image with global 64-bit integer atomics -- integer sums do not depend on the
+// order, so the gradient is bit-reproducible.  A frame has ~3 10^5 rays (3.5 M atomics, microseconds at the fabric's ~21 G/s): the record /
+// bin / band machinery, built for 10^8 shading samples, would only add launches here.
+__global__ __launch_bounds__(THREADS) void env_absmax_kernel(int64_t n3, const float* __restrict__ g, uint32_t* __restrict__ gmax)
+{
+    const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    float m = i < n3 ? fabsf(g[i]) : 0.0f;
+    if (!(m == m)) m = 3.4e38f;                              // NaN: env_fixed_scale turns the whole gradient off, as for an infinite one
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0 && m > 0.0f) atomicMax(gmax, __float_as_uint(m));        // non-negative floats order like their bits
+}
+
+__global__ __launch_bounds__(THREADS) void env_background_bwd_kernel(int64_t n, const float* __restrict__ rays_d, const float* __restrict__ Rw,
+                                                                      EnvMap env, const float* __restrict__ g_out,
+                                                                      const uint32_t* __restrict__ gmax, int shift,
+                                                                      unsigned long long* __restrict__ acc64)
+{
+    const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= n) return;
+    const double S = env_fixed_scale(*gmax, shift);
+    if (S == 0.0) return;
+    const float d[3] = {rays_d[i * 3], rays_d[i * 3 + 1], rays_d[i * 3 + 2]};
+    float dw[3];
+    dirs_s2w(d, Rw, dw);
+    int x0, x1, y0, y1;
+    float ax, ay;
+    env_footprint(env, dw, x0, x1, y0, y1, ax, ay);          // indices wrapped / clamped into [0, W) x [0, H)
+    const float w00 = (1 - ax) * (1 - ay), w10 = ax * (1 - ay), w01 = (1 - ax) * ay, w11 = ax * ay;
+    const int W = env.W;
+    auto add = [&](int64_t e, float v) { atomicAdd(&acc64[e], (unsigned long long)__double2ll_rn((double)v * S)); };
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float g = g_out[i * 3 + c];
+        if (g == 0.0f) continue;
+        add(((int64_t)y0 * W + x0) * 3 + c, w00 * g);
+        add(((int64_t)y0 * W + x1) * 3 + c, w10 * g);
+        add(((int64_t)y1 * W + x0) * 3 + c, w01 * g);
+        add(((int64_t)y1 * W + x1) * 3 + c, w11 * g);
+    }
+}
+
 }  // namespace
 
 IA_EXPORT int ia_pbr_shade(int mode, int64_t F, const float* normal, const float* albedo, const float* roughness,
@@ -953,6 +1025,45 @@ IA_EXPORT int ia_envlight_eval(int64_t n, const float* dirs_world, const float* 
     EnvMap e{env_base, env_pmf, env_h, env_w};
     env_eval_kernel<<<ia::cdiv(n, THREADS), THREADS, 0, (hipStream_t)stream>>>(n, dirs_world, e, rgb, pdf);
     return ia::check_launch("ia_envlight_eval");
+}
+
+IA_EXPORT int ia_transform_dirs_s2w(int64_t n, const float* dirs_smpl, const float* w2s_rot, float* dirs_world, ia_stream_t stream)
+{
+    if (n == 0) return IA_OK;
+    EnvMap e{nullptr, nullptr, 1, 1};
+    env_background_kernel<<<ia::cdiv(n, THREADS), THREADS, 0, (hipStream_t)stream>>>(n, dirs_smpl, w2s_rot, e, nullptr, dirs_world);
+    return ia::check_launch("ia_transform_dirs_s2w");
+}
+
+IA_EXPORT int ia_envlight_background(int64_t n, const float* rays_d_smpl, const float* w2s_rot, const float* env_base, int env_h, int env_w,
+                                     float* out, ia_stream_t stream)
+{
+    if (n == 0) return IA_OK;
+    IA_REQUIRE(env_h > 0 && env_w > 0, "environment map must be non-empty");
+    EnvMap e{env_base, nullptr, env_h, env_w};
+    env_background_kernel<<<ia::cdiv(n, THREADS), THREADS, 0, (hipStream_t)stream>>>(n, rays_d_smpl, w2s_rot, e, out, nullptr);
+    return ia::check_launch("ia_envlight_background");
+}
+
+IA_EXPORT int ia_envlight_background_bwd(int64_t n, const float* rays_d_smpl, const float* w2s_rot, const float* g_out, int env_h, int env_w,
+                                         float* g_base, int64_t* acc /*[H,W,3]*/, uint32_t* gmax /*[1]*/, ia_stream_t stream)
+{
+    if (n == 0) return IA_OK;
+    IA_REQUIRE(env_h > 0 && env_w > 0, "environment map must be non-empty");
+    IA_REQUIRE(n < ((int64_t)1 << 40), "ia_envlight_background_bwd: n must stay below 2^40");
+    IA_REQUIRE(g_base && acc && gmax, "g_base [H,W,3] float, acc [H,W,3] int64 and gmax [1] uint32 are required");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n_img = (int64_t)env_h * env_w * 3;
+    int fx_shift = 62;                                          // 62 - ceil(log2 n): see env_fixed_scale
+    for (int64_t f = 1; f < n; f <<= 1) fx_shift--;
+    (void)hipMemsetAsync(gmax, 0, 4, s);
+    (void)hipMemsetAsync(acc, 0, (size_t)n_img * 8, s);
+    EnvMap e{nullptr, nullptr, env_h, env_w};
+    unsigned long long* acc64 = reinterpret_cast<unsigned long long*>(acc);
+    env_absmax_kernel<<<ia::cdiv(3 * n, THREADS), THREADS, 0, s>>>(3 * n, g_out, gmax);
+    env_background_bwd_kernel<<<ia::cdiv(n, THREADS), THREADS, 0, s>>>(n, rays_d_smpl, w2s_rot, e, g_out, gmax, fx_shift, acc64);
+    env_fixed_finish_kernel<<<ia::cdiv(n_img, THREADS), THREADS, 0, s>>>(n_img, acc64, gmax, fx_shift, g_base);
+    return ia::check_launch("ia_envlight_background_bwd");
 }
 
 IA_EXPORT int ia_scatterer_sample(int64_t F, int lobes, const float* normal, const float* wi, const float* alpha, const float* u,

@@ -204,6 +204,19 @@ __global__ __launch_bounds__(THREADS) void vi_composite_bwd_T_kernel(int64_t n_r
     g_T[r] = has ? b0 * g_rgb[3 * r] + b1 * g_rgb[3 * r + 1] + b2 * g_rgb[3 * r + 2] : 0.0f;
 }
 
+// g_bg[r] = c_r g_rgb[r], c_r = the factor vi_composite_kernel multiplied the per-ray background with: 1 on a ray without re-samples,
+// T[r] where some re-samples fell into the background, 0 otherwise
+__global__ __launch_bounds__(THREADS) void vi_composite_bwd_bg_kernel(int64_t n_rays, const int32_t* __restrict__ rpi,
+                                                                       const int32_t* __restrict__ bg_cnt,
+                                                                       const float* __restrict__ transmittance,
+                                                                       const float* __restrict__ g_rgb, float* __restrict__ g_bg)
+{
+    const int64_t r = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (r >= n_rays) return;
+    const float c = rpi[2 * r + 1] <= 0 ? 1.0f : (bg_cnt[r] > 0 ? transmittance[r] : 0.0f);
+    g_bg[3 * r] = c * g_rgb[3 * r]; g_bg[3 * r + 1] = c * g_rgb[3 * r + 1]; g_bg[3 * r + 2] = c * g_rgb[3 * r + 2];
+}
+
 // ---- per-ray permutation of [0, spp): argsort of uniforms, ties by index (stable) -----------------------------------
 // one workgroup per ray; bitonic sort of 64-bit keys (float bits << 32 | index) in LDS; uniforms are in [0, 1) so the
 // IEEE bit pattern orders like the value.  Only the first fg_ray_cnt[r] entries of the permutation are consumed.
@@ -562,6 +575,15 @@ IA_EXPORT int ia_vi_composite_bwd(int64_t n_rays, int64_t F, const int32_t* rpi,
         vi_composite_bwd_T_kernel<<<ia::cdiv(n_rays, THREADS), THREADS, 0, s>>>(n_rays, rpi, bg_cnt, background, background_rays, g_rgb,
                                                                                 g_transmittance);
     return ia::check_launch("ia_vi_composite_bwd");
+}
+
+IA_EXPORT int ia_vi_composite_bwd_bg(int64_t n_rays, const int32_t* rpi, const int32_t* bg_cnt, const float* transmittance,
+                                     const float* g_rgb, float* g_background_rays, ia_stream_t stream)
+{
+    if (n_rays == 0) return IA_OK;
+    vi_composite_bwd_bg_kernel<<<ia::cdiv(n_rays, THREADS), THREADS, 0, (hipStream_t)stream>>>(n_rays, rpi, bg_cnt, transmittance, g_rgb,
+                                                                                              g_background_rays);
+    return ia::check_launch("ia_vi_composite_bwd_bg");
 }
 
 IA_EXPORT int ia_light_shuffle(int64_t n_rays, int spp, const int32_t* fg_ray_cnt, const int32_t* fg_start, const float* u,

@@ -8,6 +8,9 @@
         .full_frame(idx)                     the evaluation form: every pixel in order
         .check(batch)                        one read-back of the status word -> the reference's ValueError
     TrainingFrames.from_peoplesnapshot(root, split, start, end, skip, ...)
+    AnimationFrames.from_dir(root, betas, start, end, skip, downscale, hdri_filepath, near, far)
+        .frame(idx)                          AnimationDataset.__getitem__ (test split, datasets/animation.py:50-206) collated at batch size 1
+    animation_host(root, betas, start, end, ...)   its host-only part: files, K, translation, near / far (no GPU)
 
 A step costs torch.randint plus one kernel (csrc/data.hip: ia_sample_batch) and no host synchronisation; the samplers' index lists
 (np.where(mask), np.where(mask_o - mask_i)) are built once per dataset in the constructor, whose one read-back sizes them.
@@ -294,3 +297,101 @@ class TrainingFrames:
         if images.shape[1:3] != (H, W):
             raise ValueError(f"images are {images.shape[1:3]}, cameras.npz says {(H, W)}")
         return cls(torch.from_numpy(images).to(device), torch.from_numpy(masks).to(device), K, c2w, smpl, sampler, near, far)
+
+
+# ----------------------------------------------------------------------------- datasets/animation.py (test split)
+def animation_host(root: str, betas, start: int, end: int, skip: int = 1, downscale=1, near=None, far=None) -> Dict:
+    """the host-only part of AnimationDataset.__init__ / __getitem__ (datasets/animation.py:50-206, split 'test'): cameras.npz and
+    poses.npz, K = diag(2000, 2000, 1) with the principal point (height // 2, width // 2) -- in that order, as the reference writes it --,
+    the downscale, transl = trans - trans[0] + (0, 0.15, 5), the [start:end+1:skip] slice, near / far.  No GPU.
+    -> dict(K [3,3] float64, height, width, w2c [F,4,4] float32 (a single [4,4] extrinsic repeated), per_frame_extrinsic, betas [1,10],
+    body_pose [F,69], global_orient [F,3], transl [F,3], near [F], far [F] float32)."""
+    cameras = dict(np.load(os.path.join(root, "cameras.npz")))
+    per_frame = cameras["extrinsic"].ndim == 3
+    if per_frame:                                                   # height / width are arrays then: the reference takes element 0
+        height, width = cameras["height"][0], cameras["width"][0]
+    else:
+        height, width = cameras["height"], cameras["width"]
+    K = np.eye(3)
+    K[0, 0] = K[1, 1] = 2000
+    K[0, 2] = height // 2
+    K[1, 2] = width // 2
+    if downscale > 1:
+        height, width = int(height / downscale), int(width / downscale)
+        K[:2] /= downscale
+    sel = slice(start, end + 1, skip)
+    p = dict(np.load(os.path.join(root, "poses.npz")))
+    thetas = p["poses"][..., :72]
+    transl = p["trans"] - p["trans"][0:1]
+    transl += (0, 0.15, 5)
+    smpl = dict(body_pose=thetas[..., 3:].astype(np.float32)[sel], global_orient=thetas[..., :3].astype(np.float32)[sel],
+                transl=transl.astype(np.float32)[sel])
+    F = len(smpl["global_orient"])
+    ext = cameras["extrinsic"]
+    w2c = ext[sel].astype(np.float32) if per_frame else np.repeat(ext.astype(np.float32)[None], F, 0)
+    if per_frame and len(w2c) != F:
+        raise ValueError(f"{len(w2c)} extrinsics for {F} poses in [{start}:{end + 1}:{skip}]")
+    if near is not None and far is not None:
+        near_tab, far_tab = np.ones(F, np.float32) * near, np.ones(F, np.float32) * far
+    else:
+        dist = np.array([np.sqrt(np.square(smpl["transl"][i]).sum(-1)) for i in range(F)], np.float32)
+        near_tab, far_tab = dist - 1, dist + 1
+    return dict(K=K, height=int(height), width=int(width), w2c=np.ascontiguousarray(w2c), per_frame_extrinsic=bool(per_frame),
+                betas=np.asarray(betas).astype(np.float32).reshape(1, 10), near=near_tab.astype(np.float32), far=far_tab.astype(np.float32),
+                **smpl)
+
+
+class AnimationFrames:
+    """AnimationDataset, test split, on the device: a motion (poses.npz) seen by one camera or one camera per frame (cameras.npz), lit by
+    one HDRI.  `host`: animation_host(...); hdri: [1024,2048,3] float32 (io_formats.load_hdri_2k) or None."""
+
+    def __init__(self, host: Dict, hdri: Optional[np.ndarray] = None, device="cuda"):
+        self.device = _need_gpu(device)
+        self.host = host
+        self.H, self.W, self.F = host["height"], host["width"], len(host["global_orient"])
+        self.img_wh = (self.W, self.H)
+        dev = self.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)      # noqa: E731
+        self.betas, self.body_pose, self.global_orient, self.transl = (up(host[k]) for k in ("betas", "body_pose", "global_orient", "transl"))
+        self.w2c, self.near, self.far = up(host["w2c"]), up(host["near"]), up(host["far"])
+        self.index = torch.arange(self.F, dtype=torch.int64, device=dev)
+        self.hdri = None if hdri is None else up(np.asarray(hdri, np.float32))[None]        # loaded once, shared by the frames
+        self._rays = {}
+
+    @classmethod
+    def from_dir(cls, root: str, betas, start: int, end: int, skip: int = 1, downscale=1, hdri_filepath: Optional[str] = None, near=None,
+                 far=None, device="cuda") -> "AnimationFrames":
+        hdri = None
+        if hdri_filepath is not None:
+            assert os.path.exists(hdri_filepath), "HDRI not found: {}".format(hdri_filepath)
+            from . import io_formats
+            hdri = io_formats.load_hdri_2k(hdri_filepath)
+        return cls(animation_host(root, betas, start, end, skip, downscale, near, far), hdri, device)
+
+    def __len__(self):
+        return self.F
+
+    def frame(self, idx: int) -> Dict[str, Tensor]:
+        """the datum of frame idx with the leading dimension of a batch_size-1 DataLoader: rays_o, rays_d [1,HW,3], betas [1,10],
+        global_orient [1,3], body_pose [1,69], transl [1,3], index [1] int64, w2c [1,4,4], near, far [1,HW], hdri [1,1024,2048,3] when a file
+        was given.  Rays: ia_make_rays with the frame's c2w = inv(w2c) (float32, as the reference inverts it); a single extrinsic's rays
+        are made once."""
+        idx = int(idx)
+        if not 0 <= idx < self.F:
+            raise IndexError(f"frame {idx} outside [0, {self.F})")
+        key = idx if self.host["per_frame_extrinsic"] else 0
+        if key not in self._rays:
+            if len(self._rays) >= 4:
+                self._rays.pop(next(iter(self._rays)))
+            c2w = np.linalg.inv(self.host["w2c"][idx])                  # float32
+            o, d = make_rays(self.host["K"], c2w, self.H, self.W, self.device)
+            self._rays[key] = (o.reshape(1, -1, 3), d.reshape(1, -1, 3))
+        rays_o, rays_d = self._rays[key]
+        s = slice(idx, idx + 1)
+        n = self.H * self.W
+        out = dict(rays_o=rays_o, rays_d=rays_d, betas=self.betas, global_orient=self.global_orient[s], body_pose=self.body_pose[s],
+                   transl=self.transl[s], index=self.index[s], w2c=self.w2c[s], near=self.near[s, None].expand(1, n),
+                   far=self.far[s, None].expand(1, n))
+        if self.hdri is not None:
+            out["hdri"] = self.hdri
+        return out

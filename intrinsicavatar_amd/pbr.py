@@ -147,6 +147,12 @@ class EnvironmentLightTensor(torch.nn.Module):
     def eval(self, d_world: Tensor) -> Tensor:
         return self._eval(d_world, True, False)[0]
 
+    def background(self, rays_d_smpl: Tensor, w2s_rot: Tensor, env_base: Optional[Tensor] = None) -> Tensor:
+        """add_emitter (models/intrinsic_avatar.py:1319-1333): the map's radiance along camera rays given in SMPL space, [n,3]
+        (ia_envlight_background: transform_dirs_s2w + the bilinear lookup of eval, one launch).  Differentiable w.r.t. the texels when
+        `env_base` (or self.base) requires grad; directions get no gradient."""
+        return emitter_background(self.base if env_base is None else env_base, rays_d_smpl, w2s_rot)
+
     def pdf(self, d_world: Tensor) -> Tensor:
         return self._eval(d_world, False, True)[1][:, None]
 
@@ -257,6 +263,58 @@ class EnvironmentLightSG(torch.nn.Module):
 
     def sample_uniform_sphere_stratified(self, n_rays: int, n_theta: int = 16, n_phi: int = 32, device=None, u: Optional[Tensor] = None):
         return self._light().sample_uniform_sphere_stratified(n_rays, n_theta, n_phi, device=device, u=u)
+
+    def background(self, rays_d_smpl: Tensor, w2s_rot: Tensor, env_base: Optional[Tensor] = None) -> Tensor:
+        """the lobes' equirect image along camera rays -- the representation the shading path looks up through `env_base=`, so background
+        and shading see one emitter.  env_base: the differentiable image of this step (generate_image()); default: the current image."""
+        return emitter_background(self.base if env_base is None else env_base, rays_d_smpl, w2s_rot)
+
+
+@torch.no_grad()
+def transform_dirs_s2w(dirs_smpl: Tensor, w2s_rot: Tensor) -> Tensor:
+    """snarf_deformer.py:154-158: normalize(d @ w2s[:3,:3]) -- the world directions ia_envlight_background looks up (same device function)."""
+    d = dirs_smpl.detach().reshape(-1, 3).float().contiguous()
+    out = torch.empty_like(d)
+    L.check(L.lib().ia_transform_dirs_s2w(L.i64(d.shape[0]), L.ptr(d), L.ptr(w2s_rot.detach().float().contiguous()), L.ptr(out), L.stream()),
+            "ia_transform_dirs_s2w")
+    return out
+
+
+class _EmitterBackground(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, env_base, rays_d, w2s_rot):
+        base = env_base.detach().float().contiguous()
+        d = rays_d.detach().reshape(-1, 3).float().contiguous()
+        rot = w2s_rot.detach().float().contiguous()
+        if tuple(rot.shape) != (3, 3):
+            raise L.IaError(f"w2s_rot must be [3,3], got {tuple(rot.shape)}")
+        H, W, _ = base.shape
+        out = torch.empty((d.shape[0], 3), device=base.device)
+        L.check(L.lib().ia_envlight_background(L.i64(d.shape[0]), L.ptr(d), L.ptr(rot), L.ptr(base), L.i32(H), L.i32(W), L.ptr(out), L.stream()),
+                "ia_envlight_background")
+        ctx.save_for_backward(d, rot)
+        ctx.hw = (H, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        d, rot = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        H, W = ctx.hw
+        n = d.shape[0]
+        g_base = L.zeros((H, W, 3), d.device)
+        if n:
+            acc = torch.empty((H, W, 3), dtype=torch.int64, device=d.device)          # the fixed-point image and the bits of max |g|
+            gmax = torch.empty(1, dtype=torch.int32, device=d.device)
+            L.check(L.lib().ia_envlight_background_bwd(L.i64(n), L.ptr(d), L.ptr(rot), L.ptr(g_out.float().contiguous()), L.i32(H), L.i32(W),
+                                                       L.ptr(g_base), L.ptr(acc), L.ptr(gmax), L.stream()), "ia_envlight_background_bwd")
+        return g_base, None, None
+
+
+def emitter_background(env_base: Tensor, rays_d_smpl: Tensor, w2s_rot: Tensor) -> Tensor:
+    """radiance of the equirect image env_base [H,W,3] along SMPL-space camera rays [n,3]; gradient flows to env_base only."""
+    return _EmitterBackground.apply(env_base, rays_d_smpl, w2s_rot)
 
 
 # ----------------------------------------------------------------------------- colour helpers of lib.torch_pbr
@@ -464,9 +522,10 @@ class VolumeInteraction:
         per-interval inputs; sets .positions / .view_dirs / .fg_src / .fg_ray (constants)."""
         return _VIGather.apply(self, rays_o, rays_d, weights, normals, albedo, roughness, metallic)
 
-    def composite(self, w_fg, Lo, transmittance, background):
-        """rgb_phys [n,3] = sum_fg w Lo + transmittance x background (models/intrinsic_avatar.py:1335-1342,1420-1466)."""
-        return _VIComposite.apply(self, w_fg, Lo, transmittance, background)
+    def composite(self, w_fg, Lo, transmittance, background, background_rays=None):
+        """rgb_phys [n,3] = sum_fg w Lo + transmittance x background (models/intrinsic_avatar.py:1335-1342,1420-1466).  background_rays
+        [n,3] (add_emitter, :1319-1333): a colour per ray instead of the constant; differentiable (ia_vi_composite_bwd_bg)."""
+        return _VIComposite.apply(self, w_fg, Lo, transmittance, background, background_rays)
 
     @torch.no_grad()
     def index_lists(self, weights: Tensor, transmittance: Tensor, want_weights: bool = True):
@@ -532,33 +591,43 @@ class _VIGather(torch.autograd.Function):
 
 class _VIComposite(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, vi, w_fg, Lo, transmittance, background):
+    def forward(ctx, vi, w_fg, Lo, transmittance, background, background_rays=None):
         dev = Lo.device
         w_fg, Lo = w_fg.detach().float().contiguous(), Lo.detach().float().contiguous()
         T = transmittance.detach().reshape(-1).float().contiguous()
         bg = background.detach().float().contiguous()
+        bgr = None
+        if background_rays is not None:
+            bgr = background_rays.detach().float().contiguous()
+            if tuple(bgr.shape) != (vi.n_rays, 3):
+                raise L.IaError(f"background_rays must be [{vi.n_rays}, 3], got {tuple(bgr.shape)}")
         rgb = torch.empty((vi.n_rays, 3), device=dev)
         L.check(L.lib().ia_vi_composite(L.i64(vi.n_rays), L.ptr(vi.resampled_packed_info), L.ptr(vi.fg_ray_cnt), L.ptr(vi.fg_start),
-                                        L.ptr(vi.bg_counts), L.ptr(w_fg), L.ptr(Lo), L.ptr(T), L.ptr(bg), L.ptr(None), L.ptr(rgb),
+                                        L.ptr(vi.bg_counts), L.ptr(w_fg), L.ptr(Lo), L.ptr(T), L.ptr(bg), L.ptr(bgr), L.ptr(rgb),
                                         L.stream()), "ia_vi_composite")
         ctx.vi = vi
         ctx.t_shape = transmittance.shape
-        ctx.save_for_backward(w_fg, Lo, bg)
+        ctx.save_for_backward(w_fg, Lo, bg, bgr, T if bgr is not None else None)
         return rgb
 
     @staticmethod
     def backward(ctx, g_rgb):
         vi = ctx.vi
-        w_fg, Lo, bg = ctx.saved_tensors
+        w_fg, Lo, bg, bgr, T = ctx.saved_tensors
         dev = Lo.device
         g_rgb = g_rgb.float().contiguous()
         g_w = torch.empty(vi.F, device=dev) if ctx.needs_input_grad[1] else None
         g_Lo = torch.empty((vi.F, 3), device=dev) if ctx.needs_input_grad[2] else None
         g_T = torch.empty(vi.n_rays, device=dev) if ctx.needs_input_grad[3] else None
         L.check(L.lib().ia_vi_composite_bwd(L.i64(vi.n_rays), L.i64(vi.F), L.ptr(vi.resampled_packed_info), L.ptr(vi.bg_counts),
-                                            L.ptr(vi.fg_ray), L.ptr(w_fg), L.ptr(Lo), L.ptr(bg), L.ptr(None), L.ptr(g_rgb), L.ptr(g_w), L.ptr(g_Lo),
+                                            L.ptr(vi.fg_ray), L.ptr(w_fg), L.ptr(Lo), L.ptr(bg), L.ptr(bgr), L.ptr(g_rgb), L.ptr(g_w), L.ptr(g_Lo),
                                             L.ptr(g_T), L.stream()), "ia_vi_composite_bwd")
-        return None, g_w, g_Lo, (g_T.reshape(ctx.t_shape) if g_T is not None else None), None
+        g_bgr = None
+        if bgr is not None and ctx.needs_input_grad[5]:
+            g_bgr = torch.empty((vi.n_rays, 3), device=dev)
+            L.check(L.lib().ia_vi_composite_bwd_bg(L.i64(vi.n_rays), L.ptr(vi.resampled_packed_info), L.ptr(vi.bg_counts), L.ptr(T),
+                                                   L.ptr(g_rgb), L.ptr(g_bgr), L.stream()), "ia_vi_composite_bwd_bg")
+        return None, g_w, g_Lo, (g_T.reshape(ctx.t_shape) if g_T is not None else None), None, g_bgr
 
 
 @torch.no_grad()

@@ -515,14 +515,17 @@ class RenderStep:
     def relight(self, rays: Tensor, material, emitter, spp: int, light_u: Tensor, shuffle_u: Tensor,
                 background_color: Optional[Tensor] = None, global_illumination: bool = False,
                 jitter: Optional[Tensor] = None, render_mode: str = "light", scatter_u: Optional[Tensor] = None,
-                return_index_lists: bool = False, albedo_only: bool = False, albedo_align_ratio: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                return_index_lists: bool = False, albedo_only: bool = False, albedo_align_ratio: Optional[Tensor] = None,
+                add_emitter: bool = False) -> Dict[str, Tensor]:
         """forward_ with enable_phys and render_mode='light' (BASELINE configs 3 / 5):
         rendering_with_normals_mats_sdf (volrend.py:810-1020) -> sample_volume_interaction (pbr/utils.py:70-229)
         -> per-ray shuffled light directions (:1356-1378) -> secondary rays (:396-545) -> pbr_light_forward (:755-861)
         -> accumulate(resampled_weights, Lo) (:1427-1466).  light_u [spp,3], shuffle_u [n_rays,spp]: explicit RNG.
         albedo_align_ratio [3]: the material head's albedo is multiplied by it before it is composited AND before it is shaded
         (:1114-1115).  albedo_only (:222, :1290): the primary samples are shaded and composited, the volume-interaction / secondary-ray
-        branch is skipped -- comp_rgb_phys = comp_demod_phys = the background colour on every ray."""
+        branch is skipped -- comp_rgb_phys = comp_demod_phys = the background colour on every ray.
+        add_emitter (configs/config.yaml:58, :1319-1333, :1455-1490): background re-samples and rays without re-samples carry the
+        emitter's radiance along the camera ray (emitter.background) instead of background_color; `visibility` stays without background."""
         from . import pbr
         dfm = self.deformer
         rays_o, rays_d, far, t_starts, t_ends, ray_indices, packed_info, stats = self.sample(rays, jitter)
@@ -551,7 +554,10 @@ class RenderStep:
         out["primary_samples"] = dict(sdf_grad=d["sdf_grad"], valid=d["valid"], t_starts=t_starts, t_ends=t_ends, ray_indices=ray_indices)
         extras = dict(weights=weights, sdf=d["sdf"], alphas=alphas, normals=normal_smpl, albedo=mats[:, :3],
                       roughness=mats[:, 3:4], metallic=mats[:, 4:5])
-        rgb_phys = background_color[None].expand(n_rays, 3).clone()
+        # add_emitter: the three branches that take the emitter on every ray (albedo_only, no samples, no foreground re-sample: :1467-1490)
+        # keep this initial value; the composite below multiplies it with c_r per ray
+        bg_rays = emitter.background(rays_d, w2s_rot) if add_emitter else None
+        rgb_phys = bg_rays.clone() if add_emitter else background_color[None].expand(n_rays, 3).clone()
         demod_phys = rgb_phys.clone()
         if render_mode == "uniform_light":
             out["visibility"] = torch.zeros((n_rays, 1), device=dev)                      # :1266-1267
@@ -608,14 +614,15 @@ class RenderStep:
                 else:
                     raise NotImplementedError(f"Render mode {render_mode} not supported.")
                 # Lo.scatter_(bg_indices, background) + accumulate_along_rays(resampled_weights, Lo) (:1335-1342,:1420-1466)
-                rgb_phys = vi.composite(w_fg, fg_Lo, transmittance, background_color)
-                demod_phys = vi.composite(w_fg, fg_demod.contiguous(), transmittance, background_color)     # Lo_demod = Lo_diff + Lo_spec (:1421-1436)
+                rgb_phys = vi.composite(w_fg, fg_Lo, transmittance, background_color, bg_rays)
+                demod_phys = vi.composite(w_fg, fg_demod.contiguous(), transmittance, background_color, bg_rays)     # Lo_demod = Lo_diff + Lo_spec (:1421-1436)
                 out["secondary_tr"], out["fg_Lo"] = sec_tr, fg_Lo
                 if render_mode in ("light", "uniform_light"):
                     out["secondary_rgb"] = sec_rgb
                 out["fg_extras"] = dict(positions=pos, normals=nrm, albedo=alb, roughness=rough, metallic=metal, t_dirs=view)
             out["resampled_packed_info"] = vi.resampled_packed_info
             out["sampled_indices"] = vi.sampled_idx            # source interval of every re-sample (K1's `indices`): a reference, no launch
+            out["bg_counts"] = vi.bg_counts                    # background re-samples per ray (with resampled_packed_info: the factor c_r of the background)
             if return_index_lists:
                 fg_idx, bg_idx, rri, rw = vi.index_lists(weights, transmittance)
                 out.update(resampled_ray_indices=rri, resampled_weights=rw, fg_indices=fg_idx, bg_indices=bg_idx)
@@ -660,24 +667,25 @@ class RenderStep:
     def forward_(self, rays: Tensor, material, emitter, spp: int, light_u: Tensor, shuffle_u: Optional[Tensor] = None,
                  background_color: Optional[Tensor] = None, global_illumination: bool = False, render_mode: str = "light",
                  scatter_u: Optional[Tensor] = None, jitter: Optional[Tensor] = None, albedo_only: bool = False,
-                 albedo_align_ratio: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                 albedo_align_ratio: Optional[Tensor] = None, add_emitter: bool = False) -> Dict[str, Tensor]:
         """IntrinsicAvatarModel.forward_ in eval mode with enable_phys (models/intrinsic_avatar.py:950-1651): relight() + the
         reference's output dict.  Random tensors are explicit.  albedo_only / albedo_align_ratio: the two model
-        switches of the reference's test step (relight())."""
+        switches of the reference's test step (relight()); add_emitter: model.add_emitter (relight())."""
         if background_color is None:
             background_color = torch.ones(3, device=rays.device)
         o = self.relight(rays, material, emitter, spp, light_u, shuffle_u, background_color=background_color,
                          global_illumination=global_illumination, jitter=jitter, render_mode=render_mode, scatter_u=scatter_u,
-                         albedo_only=albedo_only, albedo_align_ratio=albedo_align_ratio)
+                         albedo_only=albedo_only, albedo_align_ratio=albedo_align_ratio, add_emitter=add_emitter)
         return self.output_dict(o, background_color, render_mode, o["stats"]["n_samples"])
 
     def forward_train_(self, rays: Tensor, material, emitter, spp: int, light_u: Optional[Tensor], jitter: Optional[Tensor] = None,
                        material_jitter: Optional[Tensor] = None, background_color: Optional[Tensor] = None,
                        global_illumination: bool = False, render_mode: str = "light", shuffle_u: Optional[Tensor] = None,
-                       env_base: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                       env_base: Optional[Tensor] = None, add_emitter: bool = False) -> Dict[str, Tensor]:
         """forward_ in train() mode (differentiable; the caller takes losses of the returned maps): stratified near plane
         (`jitter`), material jitter pass (`material_jitter` ~ N(0,1), :1116-1140), per-point light directions for render_mode
-        'light' (:772-781), and the training keys of the output dict (:1519-1597)."""
+        'light' (:772-781), and the training keys of the output dict (:1519-1597).  add_emitter: the differentiable emitter background
+        (from env_base when given, else the emitter's image) behind background re-samples and on empty rays."""
         from . import train_phys
         if background_color is None:
             background_color = torch.ones(3, device=rays.device)
@@ -685,7 +693,7 @@ class RenderStep:
         res = train_phys.shade_differentiable_phys(
             self, material, emitter, rays_o, rays_d, ray_indices, t_starts, t_ends, packed_info, spp, light_u, shuffle_u,
             render_mode=render_mode, env_base=env_base, background_color=background_color, global_illumination=global_illumination,
-            jitter_n=material_jitter, light_sampling="per_point" if render_mode == "light" else "shared")
+            jitter_n=material_jitter, light_sampling="per_point" if render_mode == "light" else "shared", add_emitter=add_emitter)
         d = self._training_dict(res, rays.shape[0], far, t_starts, t_ends, ray_indices, packed_info, background_color, render_mode)
         d["stats"] = dict(res["stats"], **stats)
         return d
@@ -699,7 +707,7 @@ class RenderStep:
         o = dict(res, depth=depth + T.detach() * far[:, None], comp_demod_phys=res["comp_rgb_phys"])
         if "volume_interaction" in res:
             o["comp_demod_phys"] = res["volume_interaction"].composite(res["fg_weights"], (res["fg_Lo_diff"] + res["fg_Lo_spec"]).contiguous(),
-                                                                       T, background_color)
+                                                                       T, background_color, res.get("background_rays"))
         z1 = torch.zeros((n_rays, 1), device=dev)
         o.update(sdf_samples=res["sdf"], sdf_grad_samples=res["sdf_grad"], sdf_laplace_samples=torch.zeros_like(res["sdf"]),
                  points=mid, intervals=t_ends - t_starts, ray_indices=ray_indices)

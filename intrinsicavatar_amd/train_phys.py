@@ -149,14 +149,17 @@ def shade_differentiable_phys(rs, material, emitter, rays_o: Tensor, rays_d: Ten
                               t_ends: Tensor, packed_info: Tensor, spp: int, light_u: Tensor, shuffle_u: Tensor,
                               render_mode: str = "uniform_light", env_base: Optional[Tensor] = None,
                               background_color: Optional[Tensor] = None, global_illumination: bool = False,
-                              jitter_n: Optional[Tensor] = None, light_sampling: str = "shared") -> Dict[str, Tensor]:
+                              jitter_n: Optional[Tensor] = None, light_sampling: str = "shared",
+                              add_emitter: bool = False) -> Dict[str, Tensor]:
     """differentiable rgb_normal_mats_alpha_fn + rendering_with_normals_mats_sdf + volume scattering.
     jitter_n [n_samples,3]: standard-normal noise of the material jitter pass (torch.randn_like in the reference,
     :1116-1140): materials are re-evaluated at x_cano + 0.01 * jitter_n for the relative smoothness maps (:1546-1597).
     light_sampling (render_mode 'light' only): 'shared' = the eval form of pbr_light_forward (:777-786): ONE set of spp
     light directions per frame (light_u [spp,3]) permuted per ray (shuffle_u [n_rays,spp]); 'per_point' = the training form
     (:772-776, `self.training`): an independent emitter.sample() per foreground point -- light_u is then [>= n_fg, 3]
-    uniforms (or None: drawn on the device) and shuffle_u is not used."""
+    uniforms (or None: drawn on the device) and shuffle_u is not used.
+    add_emitter (model.add_emitter, :1319-1333, :1455-1490): background re-samples and rays without re-samples carry the emitter's radiance
+    along the camera ray -- from env_base when given, else the emitter's image -- and the emitter receives their gradient."""
     dfm, geo, rad = rs.deformer, rs.geometry, rs.radiance
     n_rays = packed_info.shape[0]
     dev = rays_o.device
@@ -212,6 +215,10 @@ def shade_differentiable_phys(rs, material, emitter, rays_o: Tensor, rays_d: Ten
     if background_color is None:
         background_color = torch.ones(3, device=dev)
     rgb_phys = background_color[None].expand(n_rays, 3)
+    bg_rays = None
+    if add_emitter:
+        rgb_phys = bg_rays = emitter.background(rays_d, w2s_rot, env_base=env_base)
+        res["background_rays"] = bg_rays
     stats = dict(n_resampled=0, n_fg=0, n_secondary=0)
     if ray_indices.numel() > 0:
         vi = pbr.VolumeInteraction(ray_indices, t_starts, t_ends, n_rays, spp, weights, sdf)
@@ -244,7 +251,7 @@ def shade_differentiable_phys(rs, material, emitter, rays_o: Tensor, rays_d: Ten
                 w2s_rot, inv_pdf=inv_pdf, env_base=env_base)
             # background re-samples carry the background colour (Lo.scatter_(0, bg_indices, background_color), :1335-1342),
             # their weights sum to the ray's transmittance; rays without samples show the background (:1452-1466)
-            rgb_phys = vi.composite(w_fg, fg_Lo, 1.0 - res["opacity"], background_color)
+            rgb_phys = vi.composite(w_fg, fg_Lo, 1.0 - res["opacity"], background_color, bg_rays)
             res.update(fg_Lo=fg_Lo, fg_Lo_diff=fg_Ld, fg_Lo_spec=fg_Ls, fg_weights=w_fg, secondary_tr=sec_tr, secondary_rgb=sec_rgb,
                        out_dirs=out_dirs, inv_pdf=inv_pdf, volume_interaction=vi, fg_normals=nrm)
     res.update(comp_rgb_phys=rgb_phys, stats=stats)
@@ -278,12 +285,14 @@ def training_loss_phys(out: Dict[str, Tensor], target_rgb: Tensor, target_mask: 
     return loss
 
 
-def reference_training_loss(out: Dict[str, Tensor], rgb: Tensor, alpha: Optional[Tensor], lam: Dict[str, float], material):
+def reference_training_loss(out: Dict[str, Tensor], rgb: Tensor, alpha: Optional[Tensor], lam: Dict[str, float], material,
+                            rgb_wo_mask: Optional[Tensor] = None):
     """IntrinsicAvatarSystem.training_step (systems/intrinsic_avatar.py:160-301) on the model's output dict (RenderStep._training_dict /
     forward_train_): every term the reference logs, weighted by `lam` (the `system.loss` section of configs/config.yaml:87-109 with the
     schedules already evaluated: plain floats; a term whose weight is 0 or missing is not added).  -> (loss, {term: value}).
       rgb_l1 / rgb_mse            :165-178   sRGB image over rays_valid_full
-      rgb_phys_l1 / rgb_phys_mse  :181-212   physically based image over rays_valid_phys_full (add_emitter False)
+      rgb_phys_l1 / rgb_phys_mse  :181-212   physically based image over rays_valid_phys_full against `rgb` (add_emitter False);
+                                             rgb_wo_mask given (add_emitter True, :184-203): over ALL rays against the unmasked image
       rgb_demodulated             :217-224   luma of the demodulated image against the target's channel maximum
       eikonal                     :235-239   mean over ALL samples of (|grad sdf| - 1)^2
       mask_bce / mask_mse, opaque :242-257   clamped opacity against the batch's alpha
@@ -294,8 +303,12 @@ def reference_training_loss(out: Dict[str, Tensor], rgb: Tensor, alpha: Optional
     t = {}
     t["rgb_mse"] = F_.mse_loss(out["comp_rgb_full"][v], rgb[v])
     t["rgb_l1"] = F_.l1_loss(out["comp_rgb_full"][v], rgb[v])
-    t["rgb_phys_mse"] = F_.mse_loss(out["comp_rgb_phys_full"][vp], rgb[vp])
-    t["rgb_phys_l1"] = F_.l1_loss(out["comp_rgb_phys_full"][vp], rgb[vp])
+    if rgb_wo_mask is not None:
+        t["rgb_phys_mse"] = F_.mse_loss(out["comp_rgb_phys_full"], rgb_wo_mask)
+        t["rgb_phys_l1"] = F_.l1_loss(out["comp_rgb_phys_full"], rgb_wo_mask)
+    else:
+        t["rgb_phys_mse"] = F_.mse_loss(out["comp_rgb_phys_full"][vp], rgb[vp])
+        t["rgb_phys_l1"] = F_.l1_loss(out["comp_rgb_phys_full"][vp], rgb[vp])
     t["rgb_demodulated"] = F_.l1_loss(pbr.luma(out["comp_demod_phys_full"][vp]), pbr.max_value(rgb[vp]))
     t["eikonal"] = ((torch.linalg.norm(out["sdf_grad_samples"], ord=2, dim=-1) - 1.0) ** 2).mean()
     if alpha is not None:
