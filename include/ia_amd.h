@@ -865,6 +865,25 @@ int ia_sample_batch(int64_t n, int64_t num_mask, int64_t num_edge, int64_t frame
                     const int32_t* edge_loc, const double* cam_host, const float* near_tab, const float* far_tab, int64_t* indices,
                     float* alpha, float* rgb, float* rays_o, float* rays_d, float* near, float* far, int32_t* status, ia_stream_t stream);
 
+/* Ground-truth frames (csrc/data.hip): the albedo / normal / valid-mask part of RANADataset / SyntheticHumanDataset.__getitem__
+ * (datasets/rana.py:147-228, datasets/synthetichuman.py:156-240).  Conventions: csrc/data_math.h and DESIGN.md "Ground-truth frames".
+ *
+ * ia_truth_valid_rect: masks [F,H,W] fp32 -> rect [F,4] int32 = (x, y, w, h) of cv2.boundingRect(cv2.dilate(msk.astype(uint8),
+ *   ones(k, k))): the bounding rectangle of the pixels with mask >= 1 grown by k - 1 - k/2 towards 0 and k/2 towards the far side,
+ *   clipped to the image; (0, 0, 0, 0) for a frame without such a pixel.  k >= 1.  One workgroup per frame, no atomics, no work area.
+ * ia_sample_truth: n rows of frame `frame` of albedos, normals [F,H*W,3] u8 at the pixels pixel_indices [n] int64 (NULL: pixel j of
+ *   row j, n <= H * W) -> albedo [n,3] = float32(u8 / 255.0), normal [n,3] = (float32(u8 / 255.0) - 0.5f) * 2, valid [n] bytes 0 / 1 =
+ *   the pixel lies inside rect[frame].  A row whose index is -1 (ia_sample_batch's row of an empty list) or outside the frame reads
+ *   nothing and gets zeros and valid 0.
+ * ia_downscale_center_u8 / _f32: in [F,H,W,C] u8 / [F,H,W] fp32 -> out [F,H/s,W/s,C] / [F,H/s,W/s] for an even s >= 2 that divides H
+ *   and W: the centre 2 x 2 (a b / c d) of every s x s block, (a + b + c + d + 2) >> 2 for u8 and ((a + b) + (c + d)) * 0.25f for fp32 --
+ *   cv2.resize(fx = fy = 1/s) with its default INTER_LINEAR.  Not in place. */
+int ia_truth_valid_rect(int64_t F, int H, int W, const float* masks, int k, int32_t* rect, ia_stream_t stream);
+int ia_sample_truth(int64_t n, int64_t frame, int64_t F, int H, int W, const int64_t* pixel_indices, const uint8_t* albedos,
+                    const uint8_t* normals, const int32_t* rect, float* albedo, float* normal, uint8_t* valid, ia_stream_t stream);
+int ia_downscale_center_u8(int64_t F, int H, int W, int C, int s, const uint8_t* in, uint8_t* out, ia_stream_t stream);
+int ia_downscale_center_f32(int64_t F, int H, int W, int s, const float* in, float* out, ia_stream_t stream);
+
 /* ------------------------------------------------------------------------- */
 /* Forward skinning and mesh attributes (csrc/lbs_fwd.hip, csrc/mesh_attr.hip): ForwardDeformer.forward_skinning
  * (models/deformers/fast_snarf/deformer_torch.py:127-137 with query_weights :199-210 and skinning_mask :213-227) and the area-weighted

@@ -8,7 +8,10 @@
 //            ballot + mbcnt, so both lists come out ascending.
 //   sample   one row per lane: draw -> pixel -> mask value, colour, ray, near / far.  The list sizes are read from the CSR offsets on the
 //            device; an empty list that rows were asked from sets the status word.
-// The arithmetic lives in data_math.h (replayed on the host by tests/data_harness.c).  Built with -ffp-contract=off.
+//   truth    ground-truth frames (datasets/rana.py, synthetichuman.py): one workgroup per frame bounds the mask and writes the valid
+//            rectangle (integer minima in the wave, then through LDS); one row per lane gathers albedo / normal / valid at the pixels
+//            ia_sample_batch chose; one lane per output element takes the centre 2 x 2 of an even integer downscale.
+// The arithmetic lives in data_math.h (replayed on the host by tests/data_harness.c and tests/truth_harness.c).  Built with -ffp-contract=off.
 #include "ia_common.h"
 #include "data_math.h"
 
@@ -198,6 +201,119 @@ __global__ __launch_bounds__(DT) void sample_kernel(int64_t n, int64_t num_mask,
     }
 }
 
+// ---- ground-truth frames (datasets/rana.py, datasets/synthetichuman.py): the valid rectangle, the albedo / normal / valid rows, the downscale
+__device__ __forceinline__ int wave_min(int v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const int o = __shfl_xor(v, off, 64);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+// one workgroup per frame: integer bounds of the pixels that count, reduced in the wave, then over the four waves through LDS
+__global__ __launch_bounds__(DT) void valid_rect_kernel(int H, int W, int k, const float* __restrict__ masks, int32_t* __restrict__ rect)
+{
+    __shared__ int part[DT / 64][4];
+    const int64_t N = (int64_t)H * W, f = blockIdx.x;
+    const float* __restrict__ m = masks + f * N;
+    // (xmin, ymin, -xmax, -ymax): four minima; the empty set is (W, H, 1, 1), i.e. xmax = ymax = -1
+    int b[4] = {W, H, 1, 1};
+    for (int64_t p = threadIdx.x; p < N; p += DT) {
+        if (!ia_data_mask_counts(m[p])) continue;
+        const int x = (int)(p % W), y = (int)(p / W);
+        b[0] = x < b[0] ? x : b[0];
+        b[1] = y < b[1] ? y : b[1];
+        b[2] = -x < b[2] ? -x : b[2];
+        b[3] = -y < b[3] ? -y : b[3];
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++) b[c] = wave_min(b[c]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < 4; c++) part[threadIdx.x >> 6][c] = b[c];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < DT / 64; w++)
+#pragma unroll
+            for (int c = 0; c < 4; c++) b[c] = part[w][c] < b[c] ? part[w][c] : b[c];
+        int32_t r[4];
+        ia_data_valid_rect(b[0], b[1], -b[2], -b[3], H, W, k, r);
+#pragma unroll
+        for (int c = 0; c < 4; c++) rect[4 * f + c] = r[c];
+    }
+}
+
+__global__ __launch_bounds__(DT) void sample_truth_kernel(int64_t n, int64_t frame, int64_t N, int W, const int64_t* __restrict__ pixels,
+                                                           const uint8_t* __restrict__ albedos, const uint8_t* __restrict__ normals,
+                                                           const int32_t* __restrict__ rect, float* __restrict__ albedo,
+                                                           float* __restrict__ normal, uint8_t* __restrict__ valid)
+{
+    const int64_t j = (int64_t)blockIdx.x * DT + threadIdx.x;
+    if (j >= n) return;
+    const int64_t p = pixels ? pixels[j] : j;
+    float a[3] = {0.f, 0.f, 0.f}, nr[3] = {0.f, 0.f, 0.f};
+    uint8_t v = 0;
+    if (p >= 0 && p < N) {
+        const int64_t g = frame * N + p;
+        int32_t r[4];
+#pragma unroll
+        for (int c = 0; c < 4; c++) r[c] = rect[4 * frame + c];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            a[c] = ia_data_u8(albedos[3 * g + c]);
+            nr[c] = ia_data_normal_u8(normals[3 * g + c]);
+        }
+        v = (uint8_t)ia_data_in_rect(p, W, r);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        albedo[3 * j + c] = a[c];
+        normal[3 * j + c] = nr[c];
+    }
+    valid[j] = v;
+}
+
+// in [F,H,W,C] -> out [F,Ho,Wo,C], one lane per output element (C = 1: a plain [F,H,W] array)
+template <typename T>
+__global__ __launch_bounds__(DT) void downscale_center_kernel(int64_t total, int H, int W, int C, int s, const T* __restrict__ in,
+                                                               T* __restrict__ out)
+{
+    const int64_t e = (int64_t)blockIdx.x * DT + threadIdx.x;
+    if (e >= total) return;
+    const int Ho = H / s, Wo = W / s;
+    int64_t t = e;
+    const int c = (int)(t % C);
+    t /= C;
+    const int64_t xo = t % Wo;
+    t /= Wo;
+    const int64_t yo = t % Ho, f = t / Ho;
+    const int64_t x0 = ia_data_center_src(xo, s), y0 = ia_data_center_src(yo, s);      // 0 <= x0, x0 + 1 < W; the same in y (s even, W % s == 0)
+    const int64_t at = ((f * H + y0) * W + x0) * C + c, row = (int64_t)W * C;
+    if constexpr (sizeof(T) == 1)
+        out[e] = ia_data_center_u8(in[at], in[at + C], in[at + row], in[at + row + C]);
+    else
+        out[e] = ia_data_center_f32(in[at], in[at + C], in[at + row], in[at + row + C]);
+}
+
+template <typename T>
+int downscale_center(const char* what, int64_t F, int H, int W, int C, int s, const T* in, T* out, ia_stream_t stream)
+{
+    IA_REQUIRE(F >= 0 && H > 0 && W > 0 && C >= 1, "bad extent");
+    IA_REQUIRE(s >= 2 && s % 2 == 0 && H % s == 0 && W % s == 0, "the centre rule needs an even factor that divides both sides");
+    const int64_t per = (int64_t)(H / s) * (W / s) * C;
+    IA_REQUIRE(F == 0 || per <= INT64_MAX / 4 / F, "too many elements");
+    const int64_t total = F * per;
+    if (total == 0) return IA_OK;
+    IA_REQUIRE(in && out && (const void*)in != (const void*)out, "null pointer or in-place call");
+    IA_REQUIRE((total + DT - 1) / DT <= INT32_MAX, "too many elements for one launch");
+    downscale_center_kernel<T><<<(unsigned)((total + DT - 1) / DT), DT, 0, (hipStream_t)stream>>>(total, H, W, C, s, in, out);
+    return ia::check_launch(what);
+}
+
 // per-block counts of the two lists, their exclusive scans, the scan work area; scratch 8-byte aligned
 size_t lists_layout(void* scratch, int64_t blocks, Lists* L)
 {
@@ -317,4 +433,38 @@ IA_EXPORT int ia_sample_batch(int64_t n, int64_t num_mask, int64_t num_edge, int
                                                          edge_start, mask_loc, edge_loc, load_cam(cam_host), near_tab, far_tab, indices, alpha,
                                                          rgb, rays_o, rays_d, near, far, status);
     return ia::check_launch("ia_sample_batch");
+}
+
+IA_EXPORT int ia_truth_valid_rect(int64_t F, int H, int W, const float* masks, int k, int32_t* rect, ia_stream_t stream)
+{
+    IA_REQUIRE(H > 0 && W > 0 && (int64_t)H * W <= INT32_MAX, "bad image size");
+    IA_REQUIRE(k >= 1 && F >= 0 && F <= INT32_MAX, "need a window of at least one tap and a frame count below 2^31");
+    if (F == 0) return IA_OK;
+    IA_REQUIRE(masks && rect, "null pointer");
+    valid_rect_kernel<<<(unsigned)F, DT, 0, (hipStream_t)stream>>>(H, W, k, masks, rect);
+    return ia::check_launch("ia_truth_valid_rect");
+}
+
+IA_EXPORT int ia_sample_truth(int64_t n, int64_t frame, int64_t F, int H, int W, const int64_t* pixel_indices, const uint8_t* albedos,
+                              const uint8_t* normals, const int32_t* rect, float* albedo, float* normal, uint8_t* valid, ia_stream_t stream)
+{
+    IA_REQUIRE(H > 0 && W > 0 && (int64_t)H * W <= INT32_MAX, "bad image size");
+    IA_REQUIRE(frame >= 0 && frame < F, "frame index outside the set");
+    IA_REQUIRE(n >= 0 && (pixel_indices || n <= (int64_t)H * W), "without pixel indices the rows are the frame's first n pixels");
+    if (n == 0) return IA_OK;
+    IA_REQUIRE(albedos && normals && rect && albedo && normal && valid, "null pointer");
+    IA_REQUIRE((n + DT - 1) / DT <= INT32_MAX, "too many rows");
+    sample_truth_kernel<<<(unsigned)((n + DT - 1) / DT), DT, 0, (hipStream_t)stream>>>(n, frame, (int64_t)H * W, W, pixel_indices, albedos, normals,
+                                                                                       rect, albedo, normal, valid);
+    return ia::check_launch("ia_sample_truth");
+}
+
+IA_EXPORT int ia_downscale_center_u8(int64_t F, int H, int W, int C, int s, const uint8_t* in, uint8_t* out, ia_stream_t stream)
+{
+    return downscale_center<uint8_t>("ia_downscale_center_u8", F, H, W, C, s, in, out, stream);
+}
+
+IA_EXPORT int ia_downscale_center_f32(int64_t F, int H, int W, int s, const float* in, float* out, ia_stream_t stream)
+{
+    return downscale_center<float>("ia_downscale_center_f32", F, H, W, 1, s, in, out, stream);
 }

@@ -76,3 +76,52 @@ IA_DATA_FN float ia_data_u8(uint8_t v) { return (float)((double)v / 255.0); }
 
 // the edge test of EdgeSampler.sample: np.where(mask_o - mask_i) on the float values
 IA_DATA_FN int ia_data_is_edge(float mask_i, float mask_o) { return (mask_o - mask_i) != 0.0f; }
+
+// ----------------------------------------------------------------------------- ground-truth frames (datasets/rana.py, synthetichuman.py)
+// Conventions (DESIGN.md "Ground-truth frames"):
+//   * albedo: ia_data_u8, as rgb.  normal: ((n / 255).astype(float32) - 0.5) * 2 = (ia_data_u8(v) - 0.5f) * 2.0f, both steps in float32.
+//   * valid mask: msk.astype(np.uint8) != 0.  For 0 <= m < 256 the cast truncates, so a pixel counts iff m >= 1.0f (fractions give 0).
+//     A mask value outside [0, 256) (or NaN) has no defined result in numpy's cast either; here it counts iff m >= 1.0f.
+//   * valid rectangle: the bounding rectangle of the counting pixels dilated by a k x k window with taps at -(k/2) ... k - 1 - k/2 is the
+//     source's bounding rectangle grown by k - 1 - k/2 towards 0 and by k/2 towards the far side, clipped to the image; an empty source
+//     gives (0, 0, 0, 0).  Even k is asymmetric.
+//   * downscale by an even integer s (H % s == W % s == 0): cv2.resize's default INTER_LINEAR samples midway between source pixels
+//     s * d + s/2 - 1 and s * d + s/2 on both axes.  u8: (a + b + c + d + 2) >> 2; float32: ((a + b) + (c + d)) * 0.25f.
+
+IA_DATA_FN float ia_data_normal_u8(uint8_t v) { return (ia_data_u8(v) - 0.5f) * 2.0f; }
+
+IA_DATA_FN int ia_data_mask_counts(float m) { return m >= 1.0f; }
+
+// (xmin, ymin, xmax, ymax) of the counting pixels of an H x W mask (xmax < xmin: there is none) -> rect = (x, y, w, h)
+IA_DATA_FN void ia_data_valid_rect(int xmin, int ymin, int xmax, int ymax, int H, int W, int k, int32_t rect[4])
+{
+    if (xmax < xmin || ymax < ymin) {
+        rect[0] = rect[1] = rect[2] = rect[3] = 0;
+        return;
+    }
+    const int near_side = k - 1 - k / 2, far_side = k / 2;
+    const int x0 = xmin - near_side > 0 ? xmin - near_side : 0, y0 = ymin - near_side > 0 ? ymin - near_side : 0;
+    const int x1 = xmax + far_side < W - 1 ? xmax + far_side : W - 1, y1 = ymax + far_side < H - 1 ? ymax + far_side : H - 1;
+    rect[0] = x0;
+    rect[1] = y0;
+    rect[2] = x1 - x0 + 1;
+    rect[3] = y1 - y0 + 1;
+}
+
+// valid_msk[y : y + h, x : x + w] = True, read at pixel p = y * W + x
+IA_DATA_FN int ia_data_in_rect(int64_t p, int W, const int32_t rect[4])
+{
+    const int64_t x = p % W, y = p / W;
+    return x >= rect[0] && x < (int64_t)rect[0] + rect[2] && y >= rect[1] && y < (int64_t)rect[1] + rect[3];
+}
+
+// first of the two source positions either side of the sample point of output position d (the second is the next one)
+IA_DATA_FN int64_t ia_data_center_src(int64_t d, int s) { return (int64_t)s * d + s / 2 - 1; }
+
+IA_DATA_FN uint8_t ia_data_center_u8(uint8_t a, uint8_t b, uint8_t c, uint8_t d) { return (uint8_t)(((int)a + (int)b + (int)c + (int)d + 2) >> 2); }
+
+IA_DATA_FN float ia_data_center_f32(float a, float b, float c, float d)
+{
+    const float top = a + b, bottom = c + d;
+    return (top + bottom) * 0.25f;
+}

@@ -11,6 +11,11 @@
     AnimationFrames.from_dir(root, betas, start, end, skip, downscale, hdri_filepath, near, far)
         .frame(idx)                          AnimationDataset.__getitem__ (test split, datasets/animation.py:50-206) collated at batch size 1
     animation_host(root, betas, start, end, ...)   its host-only part: files, K, translation, near / far (no GPU)
+    TruthFrames(TrainingFrames arguments, albedos=, normals=, w2c=, valid_dilate=, hdri_files=, near_far=)
+        .batch / .full_frame                 the datum of datasets/rana.py / synthetichuman.py: + albedo, normal, valid_mask, w2c (+ hdri)
+    TruthFrames.from_rana / .from_synthetichuman(data_root, subject, split, start, end, skip, ..., downscale)
+    truth_host(kind, data_root, subject, split, start, end, ...)   their host-only part (no GPU)
+    valid_rect(masks, k), downscale_center(x, s)   the constructor's passes on the device (DESIGN.md "Ground-truth frames")
 
 A step costs torch.randint plus one kernel (csrc/data.hip: ia_sample_batch) and no host synchronisation; the samplers' index lists
 (np.where(mask), np.where(mask_o - mask_i)) are built once per dataset in the constructor, whose one read-back sizes them.
@@ -395,3 +400,255 @@ class AnimationFrames:
         if self.hdri is not None:
             out["hdri"] = self.hdri
         return out
+
+
+# ----------------------------------------------------------------------------- datasets/rana.py, datasets/synthetichuman.py
+TRUTH_KINDS = {"rana": 100, "synthetichuman": 50}       # the side of the valid mask's dilate kernel (rana.py:167, synthetichuman.py:177)
+
+
+def _center_factor(downscale, height: int, width: int) -> int:
+    """the integer factor of a downscale the centre-2x2 rule serves (1: none), NotImplementedError otherwise"""
+    s = int(downscale)
+    if s != downscale or s < 1 or (s > 1 and (s % 2 or height % s or width % s)):
+        raise NotImplementedError(f"downscale {downscale} of {height} x {width}: cv2.resize is restated for 1 and for even integers that "
+                                  "divide both sides (the shipped configs use 4, 2 and 1)")
+    return s
+
+
+def truth_host(kind: str, data_root: str, subject: str, split: str, start: int, end: int, skip: int = 1, downscale=1, near=None, far=None,
+               refine: bool = False) -> Dict:
+    """the host-only part of RANADataset / SyntheticHumanDataset.__init__ and of the per-frame scalars of __getitem__ (datasets/rana.py:
+    61-124 and :208-216, datasets/synthetichuman.py:61-134 and :218-228).  No GPU.
+    -> dict(kind, root, K [3,3] float32 (rows 0-1 divided by downscale), w2c = RT [4,4] float32, c2w = inv(RT) float32, height, width
+    (downscaled), full_height, full_width, img_wh, downscale (int), img_lists, albedo_lists, normal_lists, msk_lists, hdri_files (test
+    split, else None), betas [1,10], body_pose [*,69], global_orient [*,3], transl [*,3] float32, near, far [F] float32, dilate_k)."""
+    if kind not in TRUTH_KINDS:
+        raise ValueError(f"kind must be one of {sorted(TRUTH_KINDS)}, got {kind!r}")
+    import json
+    rana = kind == "rana"
+    root = os.path.join(data_root, split, subject) if rana else os.path.join(data_root, subject)
+    with open(os.path.join(root, "cameras.json"), "r") as f:
+        camera = json.load(f)
+    cam_name = "00"
+    if not rana:
+        camera = camera[cam_name]
+    K = np.array(camera["intrinsic"], dtype=np.float32)
+    RT = np.array(camera["extrinsic"], dtype=np.float32)
+    c2w = np.linalg.inv(RT)
+    full_height, full_width = int(camera["height"]), int(camera["width"])
+    s = _center_factor(downscale, full_height, full_width)
+    height, width = full_height, full_width
+    if s > 1:
+        height, width = int(height / s), int(width / s)
+        K[:2] /= s
+    hdri_files = None
+    if split == "test":
+        with open(os.path.join(root, "hdri_files.json"), "r") as f:
+            hdri_files = [os.path.join(data_root, "hdri", name) for name in json.load(f)]
+    sel = slice(start, end + 1, skip)
+    sub = "" if rana else f"/{cam_name}"
+    img_dir = "images" if rana or split != "test" else "images_relit"
+    albedo_dir, normal_dir = ("albedos", "normals") if rana else ("albedos_png", "normals_png")
+    lists = {name: sorted(glob.glob(f"{root}/{d}{sub}/*.{ext}"))[sel]
+             for name, d, ext in (("img_lists", img_dir, "png"), ("albedo_lists", albedo_dir, "png"), ("normal_lists", normal_dir, "png"),
+                                  ("msk_lists", "masks", "npy"))}
+    if refine:
+        cached_path = os.path.join(root, "poses/anim_nerf_test.npz")
+    elif os.path.exists(os.path.join(root, f"poses/anim_nerf_{split}.npz")):
+        cached_path = os.path.join(root, f"poses/anim_nerf_{split}.npz")
+    elif os.path.exists(os.path.join(root, f"poses/{split}.npz")):
+        cached_path = os.path.join(root, f"poses/{split}.npz")
+    else:
+        cached_path = None
+    cached = bool(cached_path and os.path.exists(cached_path))
+    p = dict(np.load(cached_path if cached else os.path.join(root, "poses.npz")))
+    if "thetas" in p:
+        p["body_pose"], p["global_orient"] = p["thetas"][..., 3:], p["thetas"][..., :3]
+    smpl = {k: p[k].astype(np.float32) for k in ("betas", "body_pose", "global_orient", "transl")}
+    smpl["betas"] = smpl["betas"].reshape(1, 10)
+    if not cached:
+        smpl.update({k: smpl[k][sel] for k in ("body_pose", "global_orient", "transl")})
+    F = len(lists["img_lists"])
+    if near is not None and far is not None:
+        near_tab, far_tab = np.ones(F, np.float32) * near, np.ones(F, np.float32) * far
+    else:
+        if rana:                                                    # distance from the camera at the origin to the mid-hip
+            dist = [np.sqrt(np.square(smpl["transl"][i]).sum(-1)) for i in range(F)]
+        else:
+            camera_loc = RT[:3, :3].T @ -RT[:3, 3]
+            dist = [np.sqrt(np.square(camera_loc - smpl["transl"][i]).sum(-1)) for i in range(F)]
+        dist = np.array(dist, np.float32)
+        near_tab, far_tab = dist - 1, dist + 1
+    return dict(kind=kind, root=root, K=K, w2c=RT, c2w=c2w, height=height, width=width, full_height=full_height, full_width=full_width,
+                img_wh=(width, height), downscale=s, hdri_files=hdri_files, near=near_tab.astype(np.float32), far=far_tab.astype(np.float32),
+                dilate_k=TRUTH_KINDS[kind], **lists, **smpl)
+
+
+def downscale_center(x: Tensor, s: int) -> Tensor:
+    """cv2.resize(x, dsize=None, fx=1/s, fy=1/s) (default INTER_LINEAR) of every frame of x -- uint8 [F,H,W,C] or [F,H,W], or float32
+    [F,H,W] -- for an even s that divides H and W: the centre 2 x 2 of every s x s block (csrc/data_math.h)."""
+    if not x.is_cuda:
+        raise L.IaError("intrinsicavatar_amd operators need GPU tensors (no CPU fallback)")
+    if x.dim() not in (3, 4) or x.dtype not in (torch.uint8, torch.float32) or (x.dim() == 4 and x.dtype != torch.uint8):
+        raise TypeError(f"downscale_center needs uint8 [F,H,W,C] / [F,H,W] or float32 [F,H,W], got {x.dtype} {tuple(x.shape)}")
+    F, H, W = (int(v) for v in x.shape[:3])
+    s = _center_factor(s, H, W)
+    if s == 1:
+        raise NotImplementedError("downscale_center needs a factor above 1")
+    x = x.contiguous()
+    out = torch.empty((F, H // s, W // s) + tuple(x.shape[3:]), dtype=x.dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        if x.dtype == torch.uint8:
+            ch = int(x.shape[3]) if x.dim() == 4 else 1
+            L.check(L.lib().ia_downscale_center_u8(L.i64(F), L.i32(H), L.i32(W), L.i32(ch), L.i32(s), L.ptr(x), L.ptr(out), L.stream()),
+                    "ia_downscale_center_u8")
+        else:
+            L.check(L.lib().ia_downscale_center_f32(L.i64(F), L.i32(H), L.i32(W), L.i32(s), L.ptr(x), L.ptr(out), L.stream()),
+                    "ia_downscale_center_f32")
+    return out
+
+
+def valid_rect(masks: Tensor, k: int) -> Tensor:
+    """masks float32 [F,H,W] on the GPU -> (x, y, w, h) int32 [F,4] of cv2.boundingRect(cv2.dilate(msk.astype(np.uint8), ones(k, k))) of
+    every frame, (0, 0, 0, 0) where no pixel counts (ia_truth_valid_rect)."""
+    if not masks.is_cuda:
+        raise L.IaError("intrinsicavatar_amd operators need GPU tensors (no CPU fallback)")
+    if masks.dtype != torch.float32 or masks.dim() != 3:
+        raise TypeError(f"valid_rect needs float32 [F,H,W], got {masks.dtype} {tuple(masks.shape)}")
+    masks = masks.contiguous()
+    F, H, W = (int(v) for v in masks.shape)
+    rect = torch.empty((F, 4), dtype=torch.int32, device=masks.device)
+    with torch.cuda.device(masks.device):
+        L.check(L.lib().ia_truth_valid_rect(L.i64(F), L.i32(H), L.i32(W), L.ptr(masks), L.i32(int(k)), L.ptr(rect), L.stream()),
+                "ia_truth_valid_rect")
+    return rect
+
+
+class TruthFrames(TrainingFrames):
+    """TrainingFrames with ground truth: RANADataset / SyntheticHumanDataset on the device.  albedos, normals: uint8 [F,H,W,3] GPU tensors
+    like images; w2c [4,4] (the extrinsic); valid_dilate: the side of the valid mask's dilate kernel; hdri_files: one path per frame (the
+    test split); near_far: (near [F], far [F]) tables instead of the |transl| -+ 1 rule; img_wh: default (W, H)."""
+    HDRI_RESIDENT = 2
+
+    def __init__(self, images: Tensor, masks: Tensor, K, c2w, smpl_params: Dict, sampler=None, near=None, far=None, *, albedos: Tensor,
+                 normals: Tensor, w2c, valid_dilate: int = 100, hdri_files=None, near_far=None, img_wh=None):
+        super().__init__(images, masks, K, c2w, smpl_params, sampler, near, far)
+        for name, t in (("albedos", albedos), ("normals", normals)):
+            if not t.is_cuda:
+                raise L.IaError("intrinsicavatar_amd operators need GPU tensors (no CPU fallback)")
+            if t.dtype != torch.uint8 or t.shape != self.images.shape:
+                raise TypeError(f"{name} must be uint8 {tuple(self.images.shape)} like images, got {t.dtype} {tuple(t.shape)}")
+        self.albedos, self.normals = albedos.contiguous(), normals.contiguous()
+        w2c = _host(w2c).astype(np.float32)
+        if w2c.shape != (4, 4):
+            raise ValueError(f"w2c must be [4,4], got {w2c.shape}")
+        self.w2c = torch.from_numpy(np.ascontiguousarray(w2c)).to(self.device)[None]
+        if hdri_files is not None and len(hdri_files) != self.F:
+            raise ValueError(f"{len(hdri_files)} hdri_files for {self.F} frames")
+        self.hdri_files = None if hdri_files is None else list(hdri_files)
+        self._hdri = {}
+        if near_far is not None:
+            tabs = [np.ascontiguousarray(_host(t), dtype=np.float32).reshape(-1) for t in near_far]
+            if any(t.shape != (self.F,) for t in tabs):
+                raise ValueError(f"near_far needs two tables of {self.F} values")
+            self.near, self.far = (torch.from_numpy(t).to(self.device) for t in tabs)
+        self.img_wh = (self.W, self.H) if img_wh is None else tuple(img_wh)
+        self.valid_dilate = int(valid_dilate)
+        self.valid_rect = valid_rect(self.masks, self.valid_dilate)
+
+    def _truth(self, out: Dict[str, Tensor], idx: int, n: int, pixels: Optional[Tensor]) -> Dict[str, Tensor]:
+        dev = self.device
+        out["albedo"] = torch.empty((1, n, 3), dtype=torch.float32, device=dev)
+        out["normal"] = torch.empty((1, n, 3), dtype=torch.float32, device=dev)
+        out["valid_mask"] = torch.empty((1, n), dtype=torch.bool, device=dev)
+        with torch.cuda.device(dev):
+            L.check(L.lib().ia_sample_truth(L.i64(n), L.i64(int(idx)), L.i64(self.F), L.i32(self.H), L.i32(self.W), L.ptr(pixels),
+                                            L.ptr(self.albedos), L.ptr(self.normals), L.ptr(self.valid_rect), L.ptr(out["albedo"]),
+                                            L.ptr(out["normal"]), L.ptr(out["valid_mask"]), L.stream()), "ia_sample_truth")
+        out["w2c"] = self.w2c
+        return out
+
+    def batch(self, idx: int, generator: Optional[torch.Generator] = None, words: Optional[Tensor] = None) -> Dict[str, Tensor]:
+        """TrainingFrames.batch (the same call) + albedo, normal [1,n,3] float32, valid_mask bool at its pixel_indices and w2c [1,4,4]: the
+        train datum of datasets/rana.py / synthetichuman.py.  One more kernel on the same stream, no host synchronisation.  valid_mask is
+        [1,n,1] here, as the reference collates it (its sampler hands every extra array back as [n, -1]), and [1,n] from full_frame;
+        preprocess_data flattens both."""
+        out = super().batch(idx, generator, words)
+        out = self._truth(out, idx, int(self.sampler.num_sample), out["pixel_indices"])
+        out["valid_mask"] = out["valid_mask"][..., None]
+        return out
+
+    def full_frame(self, idx: int) -> Dict[str, Tensor]:
+        """the test datum: every pixel in order, + hdri [1,h,w,3] float32 when the frames name their HDRIs."""
+        out = self._truth(super().full_frame(idx), idx, self.H * self.W, None)
+        if self.hdri_files is not None:
+            out["hdri"] = self.hdri(self.hdri_files[int(idx)])
+        return out
+
+    def hdri(self, path: str) -> Tensor:
+        """the environment map at `path` on the device, [1,h,w,3] float32 at its own size (the reference does not resize it); at most
+        HDRI_RESIDENT maps stay resident, and frames that name one file share one tensor."""
+        if path in self._hdri:
+            self._hdri[path] = self._hdri.pop(path)                 # most recently used last
+            return self._hdri[path]
+        ext = os.path.splitext(path)[1].lower()
+        if ext == ".exr":
+            raise NotImplementedError("OpenEXR is not available in this image: convert the environment map to Radiance .hdr")
+        from . import io_formats
+        img = io_formats.load_hdr(path)
+        while len(self._hdri) >= self.HDRI_RESIDENT:
+            self._hdri.pop(next(iter(self._hdri)))
+        self._hdri[path] = torch.from_numpy(np.ascontiguousarray(img, np.float32)).to(self.device)[None]
+        return self._hdri[path]
+
+    @classmethod
+    def from_host(cls, host: Dict, sampler=None, near=None, far=None, device="cuda") -> "TruthFrames":
+        """truth_host(...)'s files read once (PNGs through PIL, masks through np.load), moved to `device` at full resolution and, for
+        downscale > 1, reduced there: images, albedos, normals as uint8, masks in the files' own type (uint8, or floating as float32) --
+        cv2.resize works on what np.load returned, before msk.astype(np.float32)."""
+        device = _need_gpu(device)
+        from PIL import Image
+        shape = (host["full_height"], host["full_width"])
+        stacks = {}
+        for name in ("img_lists", "albedo_lists", "normal_lists"):
+            a = np.stack([np.asarray(Image.open(f).convert("RGB"), np.uint8) for f in host[name]])
+            if a.shape[1:3] != shape:
+                raise ValueError(f"{name[:-6]} files are {a.shape[1:3]}, cameras.json says {shape}")
+            stacks[name] = torch.from_numpy(a).to(device)
+        raw = [np.load(f) for f in host["msk_lists"]]
+        if any(m.shape != shape for m in raw):
+            raise ValueError(f"masks are {sorted({m.shape for m in raw})}, cameras.json says {shape}")
+        s = host["downscale"]
+        if s > 1 and all(m.dtype == np.uint8 for m in raw):
+            masks = downscale_center(torch.from_numpy(np.stack(raw)).to(device), s).to(torch.float32)
+        elif s > 1 and all(m.dtype.kind == "f" for m in raw):
+            masks = downscale_center(torch.from_numpy(np.stack([m.astype(np.float32) for m in raw])).to(device), s)
+        elif s > 1:
+            raise NotImplementedError(f"downscale of masks of type {sorted({str(m.dtype) for m in raw})}: uint8 or floating point, not mixed")
+        else:
+            masks = torch.from_numpy(np.stack([m.astype(np.float32) for m in raw])).to(device)
+        if s > 1:
+            stacks = {k: downscale_center(v, s) for k, v in stacks.items()}
+        # (an optimised pose file is not sliced by the reference: frame idx reads its row idx, the rows past the frame list are never read)
+        smpl = {k: host[k] if k == "betas" else host[k][:len(raw)] for k in ("betas", "body_pose", "global_orient", "transl")}
+        explicit = near is not None and far is not None
+        return cls(stacks["img_lists"], masks, host["K"], host["c2w"], smpl, sampler, near if explicit else None, far if explicit else None,
+                   albedos=stacks["albedo_lists"], normals=stacks["normal_lists"], w2c=host["w2c"], valid_dilate=host["dilate_k"],
+                   hdri_files=host["hdri_files"], near_far=None if explicit else (host["near"], host["far"]), img_wh=host["img_wh"])
+
+    @classmethod
+    def from_rana(cls, data_root: str, subject: str, split: str, start: int, end: int, skip: int = 1, sampler=None, near=None, far=None,
+                  refine: bool = False, downscale=1, device="cuda") -> "TruthFrames":
+        """RANADataset (datasets/rana.py): data_root/split/subject with cameras.json, images/, albedos/, normals/, masks/, poses."""
+        device = _need_gpu(device)
+        return cls.from_host(truth_host("rana", data_root, subject, split, start, end, skip, downscale, near, far, refine), sampler, near, far,
+                             device)
+
+    @classmethod
+    def from_synthetichuman(cls, data_root: str, subject: str, split: str, start: int, end: int, skip: int = 1, sampler=None, near=None,
+                            far=None, refine: bool = False, downscale=1, device="cuda") -> "TruthFrames":
+        """SyntheticHumanDataset (datasets/synthetichuman.py): data_root/subject, camera "00" of cameras.json, images/00 (images_relit/00 on
+        the test split), albedos_png/00, normals_png/00, masks/00."""
+        device = _need_gpu(device)
+        return cls.from_host(truth_host("synthetichuman", data_root, subject, split, start, end, skip, downscale, near, far, refine), sampler,
+                             near, far, device)

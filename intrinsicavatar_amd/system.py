@@ -8,11 +8,14 @@
                                                             `ray_chunk` rays with the results moved to the host in evaluation, + "beta"
     evaluate_frame    systems/intrinsic_avatar.py:317-421,  the numeric part of validation_step / test_step: albedo-only pass -> ratio ->
                       :597-720                              relit pass, and the frame's metrics (metrics.py: kernels, results on the device)
+    evaluate_sequence systems/intrinsic_avatar.py:597-720,  `mode=test` over a split with ground truth (data.TruthFrames): per frame the
+                      models/intrinsic_avatar.py:281-305    pose / occupancy grid / emitter of `prepare`, then evaluate_frame
+    mean_metrics      systems/intrinsic_avatar.py:869-911   test_epoch_end: the mean of every metric over the frames, one read-back
 
 The first three are plain tensor plumbing on whatever device the batch lives on (no kernels: a few element-wise operators per frame); held to the reference's
 own functions by tests/golden/golden_system.npz (tests/golden/make_golden_system.py)."""
 from collections import defaultdict
-from typing import Callable, Dict, Optional, Tuple
+from typing import Callable, Dict, Iterable, Iterator, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -160,3 +163,63 @@ def evaluate_frame(rs, batch: Dict[str, Tensor], material, emitter, spp: int, li
         ret["albedo_psnr"] = psnr(aligned, gt_albedo, valid_mask=gt_mask)
         ret["albedo_ssim"] = ssim(img(aligned), img(gt_albedo), valid_mask=gt_mask.reshape(H, W))
     return ret, out
+
+
+def evaluate_sequence(rs, material, frames, body, spp: int, *, stage: str = "test", emitter=None, render_mode: str = "light",
+                      global_illumination: bool = True, resample_light: bool = True, generator: Optional[torch.Generator] = None,
+                      frames_idx: Optional[Iterable[int]] = None, cano_pose="da_pose", occ_res: int = 64,
+                      ray_chunk: int = 1 << 19) -> Iterator[Tuple[int, Dict[str, Tensor], Dict[str, Tensor]]]:
+    """the reference's `mode=test` over a split with ground truth: yields (idx, metrics, out) per frame of data.TruthFrames -- full_frame
+    -> animation.prepare_frame (pose, bbox, test occupancy grid, as render_sequence) -> preprocess_data(stage) -> evaluate_frame with
+    img_wh = frames.img_wh.  `out` also carries the random tensors it was made with (`light_u`, `shuffle_u`), drawn from `generator` in
+    render_sequence's order.  emitter: given, or an EnvironmentLightTensor of the frame's "hdri", rebuilt (with update_pdf) only when
+    that tensor changes (IntrinsicAvatarModel.prepare, models/intrinsic_avatar.py:286-305); resample_light=False draws light_u once.
+    mean_metrics(list of the yielded metrics) is test_epoch_end."""
+    from . import animation, smpl                                   # (animation imports this module)
+    if render_mode in ("mats", "mis"):
+        raise NotImplementedError("evaluate_sequence draws the random tensors of the light / uniform_light estimators")
+    dev = rs.deformer.device
+    dt = body.v_template.dtype
+    rest = body.forward(frames.betas[:1].to(dt), smpl.rest_pose(cano_pose, device=body.v_template.device).to(dt),
+                        torch.zeros((1, 3), dtype=dt, device=body.v_template.device))
+    A_rest_inv = torch.linalg.inv(rest["A"].float())
+    n_light = 512 if render_mode == "uniform_light" else spp
+    given, built_from, light_u = emitter, None, None
+    for idx in (range(len(frames)) if frames_idx is None else frames_idx):
+        batch = dict(frames.full_frame(idx))
+        batch.pop("pixel_indices", None)
+        batch.pop("status", None)
+        occ_rand = animation._rand((occ_res ** 3, 3, 3), dev, generator)
+        animation.prepare_frame(rs, body, A_rest_inv, batch, occ_rand, occ_res)
+        batch, bg, _ = preprocess_data(batch, stage)
+        if given is None:
+            if "hdri" not in batch:
+                raise ValueError("evaluate_sequence needs an emitter or frames whose full_frame carries an HDRI (the test split)")
+            if built_from is None or built_from.data_ptr() != batch["hdri"].data_ptr() or built_from.shape != batch["hdri"].shape:
+                built_from = batch["hdri"]
+                emitter = pbr.EnvironmentLightTensor(built_from.contiguous())
+                emitter.update_pdf()
+        rays = batch["rays"]
+        if light_u is None or resample_light:
+            light_u = animation._rand((n_light, 3), dev, generator)
+        shuffle_u = animation._rand((rays.shape[0], spp), dev, generator)
+        ret, out = evaluate_frame(rs, batch, material, emitter, spp, light_u, shuffle_u, img_wh=frames.img_wh, stage=stage, background_color=bg,
+                                  global_illumination=global_illumination, render_mode=render_mode, ray_chunk=ray_chunk)
+        out["light_u"], out["shuffle_u"] = light_u, shuffle_u
+        yield int(idx), ret, out
+
+
+def mean_metrics(per_frame) -> Dict[str, float]:
+    """test_epoch_end (systems/intrinsic_avatar.py:905-911): the mean of every metric over the frames, formed on the device (float64) and
+    read back with ONE copy for all keys; ValueError if a frame's metric could not be formed (metrics.to_host's statuses)."""
+    per_frame = list(per_frame)
+    if not per_frame:
+        return {}
+    keys = list(per_frame[0])
+    plain = lambda t: t.as_subclass(Tensor).double().reshape(-1)      # noqa: E731
+    means = [torch.stack([plain(m[k])[0] for m in per_frame]).mean() for k in keys]
+    bufs = [(k, m[k]._buf) for m in per_frame for k in keys if getattr(m[k], "_buf", None) is not None]
+    host = torch.cat([torch.stack(means)] + [plain(b)[-1:] for _, b in bufs]).cpu()
+    for (k, _), status in zip(bufs, host[len(keys):].tolist()):
+        metrics._raise_on_status(int(status), k)
+    return {k: float(v) for k, v in zip(keys, host[:len(keys)].tolist())}
