@@ -569,6 +569,53 @@ int ia_eikonal_bwd(int64_t n, const float* sdf_grad, const uint8_t* valid, const
                    ia_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
+/* The loss of one training step (IntrinsicAvatarSystem.training_step, systems/intrinsic_avatar.py:160-301) on the model's
+ * output dict: two launches forward, one backward, whichever terms are on.  Inputs are fp32 device pointers ([n_rays,3] /
+ * [n_rays] per ray, [n_samples] / [n_samples,3] per sample; the two validity masks are bytes); ANY of them may be NULL, and a
+ * term that lacks an input is absent: its slot of terms[] is 0 and it is not added.  Term order of terms[] and of the HOST
+ * array weights[IA_TRAIN_LOSS_TERMS]:
+ *    0 rgb_mse   1 rgb_l1            means of comp_rgb_full against rgb over the rays of rays_valid_full         (:167-180)
+ *    2 rgb_phys_mse  3 rgb_phys_l1   comp_rgb_phys_full against rgb over rays_valid_phys_full; rgb_wo_mask given:
+ *                                    against rgb_wo_mask over ALL rays                                            (:183-212)
+ *    4 rgb_demodulated               |channel mean of comp_demod_phys_full - channel max of rgb| over
+ *                                    rays_valid_phys_full                                                         (:217-224)
+ *    5 eikonal                       mean over all samples of (|sdf_grad| - 1)^2                                  (:235-239)
+ *    6 mask_mse  7 mask_bce  8 opaque  x = clamp(opacity, 1e-3, 1 - 1e-3) against alpha; opaque = BCE(x, x),
+ *                                    differentiated through both arguments; the clamp passes the gradient on the
+ *                                    closed interval (torch.clamp)                                                (:242-256)
+ *    9 sparsity                      mean exp(-sparsity_scale |sdf|)                                              (:259-263)
+ *   10 curvature                     mean |sdf_laplace|                                                           (:265-268)
+ *   11 normal_orientation  12 albedo_smoothness  13 roughness_smoothness  14 metallic_smoothness  means of the maps (:285-290)
+ *   15 unused
+ * A NULL validity mask counts every ray.  A mean over nothing is NaN, as in torch.  loss[0] = sum of weights[k] * terms[k] over
+ * the present terms whose weight is not 0, in this order.  Every summand is formed and summed in fp64, blocks combine in a
+ * fixed order without atomics: the same inputs give the same bits.  stats[IA_TRAIN_LOSS_STATS] = the sixteen terms in fp64,
+ * then the number of rays of rays_valid_full and of rays_valid_phys_full, which _bwd divides by.
+ * partials: ia_train_loss_partials(n_rays, n_samples) doubles, written before they are read in every call.
+ * _bwd: g_x = g_loss[0] * d loss / d x for every g_* that is not NULL (all elements are written; a term of weight 0
+ * contributes 0, so the caller passes NULL where nothing with a weight depends on x). */
+#define IA_TRAIN_LOSS_TERMS 16
+#define IA_TRAIN_LOSS_STATS 18
+int64_t ia_train_loss_partials(int64_t n_rays, int64_t n_samples);
+int ia_train_loss(int64_t n_rays, int64_t n_samples, const float* comp_rgb_full, const float* comp_rgb_phys_full,
+                  const float* comp_demod_phys_full, const float* opacity, const uint8_t* rays_valid_full,
+                  const uint8_t* rays_valid_phys_full, const float* rgb, const float* rgb_wo_mask, const float* alpha,
+                  const float* normals_orientation_loss_map, const float* albedo_smoothness_loss_map,
+                  const float* roughness_smoothness_loss_map, const float* metallic_smoothness_loss_map,
+                  const float* sdf_samples, const float* sdf_grad_samples, const float* sdf_laplace_samples,
+                  const float* weights, float sparsity_scale, float* terms, float* loss, double* stats, double* partials,
+                  ia_stream_t stream);
+int ia_train_loss_bwd(int64_t n_rays, int64_t n_samples, const float* comp_rgb_full, const float* comp_rgb_phys_full,
+                      const float* comp_demod_phys_full, const float* opacity, const uint8_t* rays_valid_full,
+                      const uint8_t* rays_valid_phys_full, const float* rgb, const float* rgb_wo_mask, const float* alpha,
+                      const float* sdf_samples, const float* sdf_grad_samples, const float* sdf_laplace_samples,
+                      const float* weights, float sparsity_scale, const double* stats, const float* g_loss,
+                      float* g_comp_rgb_full, float* g_comp_rgb_phys_full, float* g_comp_demod_phys_full, float* g_opacity,
+                      float* g_normals_orientation_loss_map, float* g_albedo_smoothness_loss_map,
+                      float* g_roughness_smoothness_loss_map, float* g_metallic_smoothness_loss_map, float* g_sdf_samples,
+                      float* g_sdf_grad_samples, float* g_sdf_laplace_samples, ia_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
 /* Optimiser step.  torch.optim.Adam exactly as the reference builds it (configs/config.yaml:110-136,
  * systems/utils.py:314-325: Adam, betas (0.9, 0.99), eps 1e-15, per-group lr and L2 weight_decay), for n_tensors
  * parameter tensors in ONE launch (40 per launch internally).  params/grads/exp_avg/exp_avg_sq/numel/step_size/

@@ -39,6 +39,7 @@ SOURCES = {
     "data.hip": ["-ffp-contract=off"],
     "lbs_fwd.hip": ["-ffp-contract=off"],
     "mesh_attr.hip": ["-ffp-contract=off"],
+    "train_loss.hip": ["-ffp-contract=off"],
 }
 
 

@@ -279,7 +279,7 @@ class RenderStep:
                               background_color: Optional[Tensor] = None, global_illumination: bool = False,
                               light_sampling: str = "shared", loss_scale: float = 1.0, retain_graph: bool = False,
                               material_jitter: Optional[Tensor] = None, loss_config: Optional[dict] = None,
-                              eik_denominator=None) -> Dict[str, Tensor]:
+                              eik_denominator=None, curv_u: Optional[Tensor] = None) -> Dict[str, Tensor]:
         """BASELINE config 4: training step with the PBR branch (material head, volume scattering, secondary rays,
         light / uniform_light estimator) -- fwd + bwd to geometry, radiance, material and environment-light parameters.
         loss_scale: weight of this ray chunk when a frame is processed in several chunks with gradient accumulation
@@ -293,14 +293,15 @@ class RenderStep:
         out["loss_terms"].  tests/test_gpu_backward_golden.py holds this call to the reference's own autograd.
         eik_denominator: None = the eikonal mean is over this call's samples; a number, or a callable n_samples -> number (e.g. an
         all-reduce of the ranks' sample counts divided by the world size), = the denominator of that mean under ray-batch sharding, so that
-        the average of the ranks' losses is the loss of the global batch (systems/intrinsic_avatar.py:235-239 takes .mean() over all samples)."""
+        the average of the ranks' losses is the loss of the global batch (systems/intrinsic_avatar.py:235-239 takes .mean() over all samples).
+        curv_u [n_samples,3]: uniforms of the curvature probe (model.with_curvature_loss): the output dict's sdf_laplace_samples."""
         from . import train_phys
         rays_o, rays_d, far, t_starts, t_ends, ray_indices, packed_info, stats = self.sample(rays, jitter)
         out = train_phys.shade_differentiable_phys(self, material, emitter, rays_o, rays_d, ray_indices, t_starts, t_ends,
                                                    packed_info, spp, light_u, shuffle_u, render_mode=render_mode,
                                                    env_base=env_base, background_color=background_color,
                                                    global_illumination=global_illumination, light_sampling=light_sampling,
-                                                   jitter_n=material_jitter)
+                                                   jitter_n=material_jitter, curv_u=curv_u)
         if loss_config is None:
             den = eik_denominator(int(t_starts.shape[0])) if callable(eik_denominator) else eik_denominator
             loss = train_phys.training_loss_phys(out, target_rgb, target_mask, **({} if den is None else dict(eik_denominator=den)))
@@ -681,11 +682,12 @@ class RenderStep:
     def forward_train_(self, rays: Tensor, material, emitter, spp: int, light_u: Optional[Tensor], jitter: Optional[Tensor] = None,
                        material_jitter: Optional[Tensor] = None, background_color: Optional[Tensor] = None,
                        global_illumination: bool = False, render_mode: str = "light", shuffle_u: Optional[Tensor] = None,
-                       env_base: Optional[Tensor] = None, add_emitter: bool = False) -> Dict[str, Tensor]:
+                       env_base: Optional[Tensor] = None, add_emitter: bool = False, curv_u: Optional[Tensor] = None) -> Dict[str, Tensor]:
         """forward_ in train() mode (differentiable; the caller takes losses of the returned maps): stratified near plane
         (`jitter`), material jitter pass (`material_jitter` ~ N(0,1), :1116-1140), per-point light directions for render_mode
         'light' (:772-781), and the training keys of the output dict (:1519-1597).  add_emitter: the differentiable emitter background
-        (from env_base when given, else the emitter's image) behind background re-samples and on empty rays."""
+        (from env_base when given, else the emitter's image) behind background re-samples and on empty rays.
+        curv_u [n_samples,3]: uniforms of the curvature probe (model.with_curvature_loss); without it sdf_laplace_samples is zero."""
         from . import train_phys
         if background_color is None:
             background_color = torch.ones(3, device=rays.device)
@@ -693,9 +695,45 @@ class RenderStep:
         res = train_phys.shade_differentiable_phys(
             self, material, emitter, rays_o, rays_d, ray_indices, t_starts, t_ends, packed_info, spp, light_u, shuffle_u,
             render_mode=render_mode, env_base=env_base, background_color=background_color, global_illumination=global_illumination,
-            jitter_n=material_jitter, light_sampling="per_point" if render_mode == "light" else "shared", add_emitter=add_emitter)
+            jitter_n=material_jitter, light_sampling="per_point" if render_mode == "light" else "shared", add_emitter=add_emitter,
+            curv_u=curv_u)
         d = self._training_dict(res, rays.shape[0], far, t_starts, t_ends, ray_indices, packed_info, background_color, render_mode)
         d["stats"] = dict(res["stats"], **stats)
+        return d
+
+    def forward_train_rf_(self, rays: Tensor, jitter: Optional[Tensor] = None, curv_u: Optional[Tensor] = None,
+                          background_color: Optional[Tensor] = None) -> Dict[str, Tensor]:
+        """forward_ in train() mode with enable_phys OFF (global_step < phys_kick_in_step; models/intrinsic_avatar.py:1492-1651):
+        the radiance-field maps of train.shade_differentiable in the reference's output dict -- no `*_phys` / material keys,
+        rays_valid_phys all false, the four loss maps zero, `_bg` and `_full` with the sRGB image over the background colour.
+        curv_u [n_samples,3]: uniforms of the curvature probe (model.with_curvature_loss); without it sdf_laplace_samples is zero."""
+        from . import pbr, train
+        if background_color is None:
+            background_color = torch.ones(3, device=rays.device)
+        rays_o, rays_d, far, t_starts, t_ends, ray_indices, packed_info, stats = self.sample(rays, jitter)
+        n_samples = int(t_starts.shape[0])
+        res = train.shade_differentiable(self, rays_o, rays_d, ray_indices, t_starts, t_ends, packed_info,
+                                         curv_u=curv_u[:n_samples] if curv_u is not None else None)
+        acc = res["opacity"]
+        n, dev = acc.shape[0], acc.device
+        bgc = background_color.to(dev).float()
+        T = 1.0 - acc
+        z1 = torch.zeros((n, 1), device=dev)
+        out = dict(comp_rgb=res["comp_rgb"], comp_normal=res["comp_normal"], opacity=acc, depth=res["depth"].detach() + T.detach() * far[:, None],
+                   rays_valid=acc > 0, rays_valid_phys=torch.zeros_like(acc, dtype=torch.bool),
+                   num_samples=torch.as_tensor([n_samples], dtype=torch.int32, device=dev),
+                   sdf_samples=res["sdf"], sdf_grad_samples=res["sdf_grad"],
+                   sdf_laplace_samples=res["sdf_laplace"] if "sdf_laplace" in res else torch.zeros_like(res["sdf"]),
+                   weights=res["weights"], points=(t_starts + t_ends) / 2.0, intervals=t_ends - t_starts, ray_indices=ray_indices,
+                   normals_orientation_loss_map=z1, albedo_smoothness_loss_map=z1, roughness_smoothness_loss_map=z1,
+                   metallic_smoothness_loss_map=z1)
+        out_bg = dict(comp_rgb=bgc[None].expand(n, 3), num_samples=torch.zeros_like(out["num_samples"]),
+                      rays_valid=torch.zeros_like(out["rays_valid"]), rays_valid_phys=torch.zeros_like(out["rays_valid_phys"]))
+        out_full = dict(comp_rgb=pbr.rgb_to_srgb(out["comp_rgb"] + out_bg["comp_rgb"] * T).clamp(0, 1),
+                        num_samples=out["num_samples"] + out_bg["num_samples"], rays_valid=out["rays_valid"] | out_bg["rays_valid"],
+                        rays_valid_phys=out["rays_valid_phys"] | out_bg["rays_valid_phys"])
+        d = {**out, **{k + "_bg": v for k, v in out_bg.items()}, **{k + "_full": v for k, v in out_full.items()}}
+        d["stats"] = dict(stats)
         return d
 
     def _training_dict(self, res, n_rays, far, t_starts, t_ends, ray_indices, packed_info, background_color, render_mode):
@@ -709,7 +747,7 @@ class RenderStep:
             o["comp_demod_phys"] = res["volume_interaction"].composite(res["fg_weights"], (res["fg_Lo_diff"] + res["fg_Lo_spec"]).contiguous(),
                                                                        T, background_color, res.get("background_rays"))
         z1 = torch.zeros((n_rays, 1), device=dev)
-        o.update(sdf_samples=res["sdf"], sdf_grad_samples=res["sdf_grad"], sdf_laplace_samples=torch.zeros_like(res["sdf"]),
+        o.update(sdf_samples=res["sdf"], sdf_grad_samples=res["sdf_grad"], sdf_laplace_samples=res["sdf_laplace"] if "sdf_laplace" in res else torch.zeros_like(res["sdf"]),
                  points=mid, intervals=t_ends - t_starts, ray_indices=ray_indices)
         for k in ("normals_orientation_loss_map", "albedo_smoothness_loss_map", "roughness_smoothness_loss_map", "metallic_smoothness_loss_map"):
             o.setdefault(k, z1)

@@ -150,7 +150,7 @@ def shade_differentiable_phys(rs, material, emitter, rays_o: Tensor, rays_d: Ten
                               render_mode: str = "uniform_light", env_base: Optional[Tensor] = None,
                               background_color: Optional[Tensor] = None, global_illumination: bool = False,
                               jitter_n: Optional[Tensor] = None, light_sampling: str = "shared",
-                              add_emitter: bool = False) -> Dict[str, Tensor]:
+                              add_emitter: bool = False, curv_u: Optional[Tensor] = None) -> Dict[str, Tensor]:
     """differentiable rgb_normal_mats_alpha_fn + rendering_with_normals_mats_sdf + volume scattering.
     jitter_n [n_samples,3]: standard-normal noise of the material jitter pass (torch.randn_like in the reference,
     :1116-1140): materials are re-evaluated at x_cano + 0.01 * jitter_n for the relative smoothness maps (:1546-1597).
@@ -159,7 +159,9 @@ def shade_differentiable_phys(rs, material, emitter, rays_o: Tensor, rays_d: Ten
     (:772-776, `self.training`): an independent emitter.sample() per foreground point -- light_u is then [>= n_fg, 3]
     uniforms (or None: drawn on the device) and shuffle_u is not used.
     add_emitter (model.add_emitter, :1319-1333, :1455-1490): background re-samples and rays without re-samples carry the emitter's radiance
-    along the camera ray -- from env_base when given, else the emitter's image -- and the emitter receives their gradient."""
+    along the camera ray -- from env_base when given, else the emitter's image -- and the emitter receives their gradient.
+    curv_u [n_samples,3]: uniforms for the curvature probe directions (model.with_curvature_loss): enables res["sdf_laplace"], as
+    train.shade_differentiable does."""
     dfm, geo, rad = rs.deformer, rs.geometry, rs.radiance
     n_rays = packed_info.shape[0]
     dev = rays_o.device
@@ -211,6 +213,8 @@ def shade_differentiable_phys(rs, material, emitter, rays_o: Tensor, rays_d: Ten
     res = dict(comp_rgb=acc(rgbs), comp_normal=acc(normal_world), opacity=acc(None), albedo=acc(albedo),
                roughness=acc(rough), metallic=acc(metal), weights=weights, alphas=alphas, sdf=sdf,
                sdf_grad=sdf_grad, valid=valid, n_samples=pts.shape[0], **extra_maps)
+    if curv_u is not None:       # laplace = 0 for points without a valid candidate (snarf_deformer.py:233-235)
+        res["sdf_laplace"] = train.curvature_laplace(geo, d["pts_cano"], grad_c, curv_u[:pts.shape[0]]) * valid.float()
     # ---- volume scattering (enable_phys)
     if background_color is None:
         background_color = torch.ones(3, device=dev)
