@@ -66,8 +66,7 @@ def make_rays(K, c2w, H: int, W: int, device) -> Tuple[Tensor, Tensor]:
     rays_o = torch.empty((H, W, 3), dtype=torch.float32, device=device)
     rays_d = torch.empty((H, W, 3), dtype=torch.float32, device=device)
     with torch.cuda.device(device):
-        L.check(L.lib().ia_make_rays(L.i64(H * W), L.ptr(None), L.i32(H), L.i32(W), camera_words(K, c2w), L.ptr(rays_o), L.ptr(rays_d),
-                                     L.stream()), "ia_make_rays")
+        L.lib().ia_make_rays(H * W, None, H, W, camera_words(K, c2w), rays_o, rays_d)
     return rays_o, rays_d
 
 
@@ -84,8 +83,7 @@ def window_minmax(x: Tensor, k: int, dim: int = -1) -> Tuple[Tensor, Tensor]:
     inner = int(np.prod(x.shape[dim + 1:], dtype=np.int64))
     lo, hi = torch.empty_like(x), torch.empty_like(x)
     with torch.cuda.device(x.device):
-        L.check(L.lib().ia_window_minmax(L.i64(outer), L.i64(x.shape[dim]), L.i64(inner), L.i32(int(k)), L.ptr(x), L.ptr(lo), L.ptr(hi),
-                                         L.stream()), "ia_window_minmax")
+        L.lib().ia_window_minmax(outer, x.shape[dim], inner, int(k), x, lo, hi)
     return lo, hi
 
 
@@ -201,21 +199,19 @@ class TrainingFrames:
     def _build_lists(self):
         F, N = self.F, self.H * self.W
         mask_i, mask_o = self.sampler.edge_band(self.masks)
-        lib, dev = L.lib(), self.device
+        dev = self.device
         with torch.cuda.device(dev):
-            st = L.stream()
-            scratch = L.work_area(lib.ia_flag_lists_scratch_bytes(L.i64(F), L.i64(N)), dev)
+            scratch = L.work_area(L.lib().ia_flag_lists_scratch_bytes(F, N), dev)
             totals = torch.empty(2, dtype=torch.int32, device=dev)
-            args = (L.i64(F), L.i64(N), L.ptr(self.masks), L.ptr(mask_i), L.ptr(mask_o), L.ptr(scratch))
-            L.check(lib.ia_flag_lists_count(*args, L.ptr(totals), st), "ia_flag_lists_count")
+            args = (F, N, self.masks, mask_i, mask_o, scratch)
+            L.lib().ia_flag_lists_count(*args, totals)
             n_mask, n_edge = (int(v) for v in totals.tolist())              # the one read-back: sizes of the two lists
             self.mask_start = torch.empty(F + 1, dtype=torch.int32, device=dev)
             self.edge_start = torch.empty(F + 1, dtype=torch.int32, device=dev)
             self.counts = torch.empty((F, 2), dtype=torch.int32, device=dev)
             self.mask_loc = torch.empty(max(n_mask, 1), dtype=torch.int32, device=dev)[:n_mask]
             self.edge_loc = torch.empty(max(n_edge, 1), dtype=torch.int32, device=dev)[:n_edge]
-            L.check(lib.ia_flag_lists_fill(*args, L.ptr(totals), L.ptr(self.mask_start), L.ptr(self.edge_start), L.ptr(self.counts),
-                                           L.ptr(self.mask_loc), L.ptr(self.edge_loc), st), "ia_flag_lists_fill")
+            L.lib().ia_flag_lists_fill(*args, totals, self.mask_start, self.edge_start, self.counts, self.mask_loc, self.edge_loc)
 
     def __len__(self):
         return self.F
@@ -229,12 +225,9 @@ class TrainingFrames:
         out = {"rgb": f32(1, n, 3), "rays_o": f32(1, n, 3), "rays_d": f32(1, n, 3), "alpha": f32(1, n), "near": f32(1, n), "far": f32(1, n),
                "pixel_indices": torch.empty((1, n), dtype=torch.int64, device=dev), "status": torch.empty(1, dtype=torch.int32, device=dev)}
         with torch.cuda.device(dev):
-            L.check(L.lib().ia_sample_batch(
-                L.i64(n), L.i64(num_mask), L.i64(num_edge), L.i64(idx), L.i64(self.F), L.i32(self.H), L.i32(self.W), L.ptr(words),
-                L.ptr(self.masks), L.ptr(self.images), L.ptr(self.mask_start), L.ptr(self.edge_start), L.ptr(self.mask_loc),
-                L.ptr(self.edge_loc), self.cam, L.ptr(self.near), L.ptr(self.far), L.ptr(out["pixel_indices"]), L.ptr(out["alpha"]),
-                L.ptr(out["rgb"]), L.ptr(out["rays_o"]), L.ptr(out["rays_d"]), L.ptr(out["near"]), L.ptr(out["far"]), L.ptr(out["status"]),
-                L.stream()), "ia_sample_batch")
+            L.lib().ia_sample_batch(n, num_mask, num_edge, idx, self.F, self.H, self.W, words, self.masks, self.images, self.mask_start,
+                                    self.edge_start, self.mask_loc, self.edge_loc, self.cam, self.near, self.far, out["pixel_indices"], out["alpha"],
+                                    out["rgb"], out["rays_o"], out["rays_d"], out["near"], out["far"], out["status"])
         s = slice(idx, idx + 1)
         out.update(betas=self.betas, global_orient=self.global_orient[s], body_pose=self.body_pose[s], transl=self.transl[s],
                    index=self.index[s], t_idx=self.t_idx[s])
@@ -500,11 +493,9 @@ def downscale_center(x: Tensor, s: int) -> Tensor:
     with torch.cuda.device(x.device):
         if x.dtype == torch.uint8:
             ch = int(x.shape[3]) if x.dim() == 4 else 1
-            L.check(L.lib().ia_downscale_center_u8(L.i64(F), L.i32(H), L.i32(W), L.i32(ch), L.i32(s), L.ptr(x), L.ptr(out), L.stream()),
-                    "ia_downscale_center_u8")
+            L.lib().ia_downscale_center_u8(F, H, W, ch, s, x, out)
         else:
-            L.check(L.lib().ia_downscale_center_f32(L.i64(F), L.i32(H), L.i32(W), L.i32(s), L.ptr(x), L.ptr(out), L.stream()),
-                    "ia_downscale_center_f32")
+            L.lib().ia_downscale_center_f32(F, H, W, s, x, out)
     return out
 
 
@@ -519,8 +510,7 @@ def valid_rect(masks: Tensor, k: int) -> Tensor:
     F, H, W = (int(v) for v in masks.shape)
     rect = torch.empty((F, 4), dtype=torch.int32, device=masks.device)
     with torch.cuda.device(masks.device):
-        L.check(L.lib().ia_truth_valid_rect(L.i64(F), L.i32(H), L.i32(W), L.ptr(masks), L.i32(int(k)), L.ptr(rect), L.stream()),
-                "ia_truth_valid_rect")
+        L.lib().ia_truth_valid_rect(F, H, W, masks, int(k), rect)
     return rect
 
 
@@ -562,9 +552,8 @@ class TruthFrames(TrainingFrames):
         out["normal"] = torch.empty((1, n, 3), dtype=torch.float32, device=dev)
         out["valid_mask"] = torch.empty((1, n), dtype=torch.bool, device=dev)
         with torch.cuda.device(dev):
-            L.check(L.lib().ia_sample_truth(L.i64(n), L.i64(int(idx)), L.i64(self.F), L.i32(self.H), L.i32(self.W), L.ptr(pixels),
-                                            L.ptr(self.albedos), L.ptr(self.normals), L.ptr(self.valid_rect), L.ptr(out["albedo"]),
-                                            L.ptr(out["normal"]), L.ptr(out["valid_mask"]), L.stream()), "ia_sample_truth")
+            L.lib().ia_sample_truth(n, int(idx), self.F, self.H, self.W, pixels, self.albedos, self.normals, self.valid_rect, out["albedo"],
+                                    out["normal"], out["valid_mask"])
         out["w2c"] = self.w2c
         return out
 

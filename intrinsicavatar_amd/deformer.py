@@ -11,7 +11,6 @@ boolean-mask index).
 """
 from typing import Optional
 
-import ctypes as C
 import os
 import threading
 
@@ -138,8 +137,7 @@ class SNARFDeformer:
                 and not w2s.requires_grad and w2s.shape == (4, 4):
             n = rays.shape[0]
             out = torch.empty((n, 8), device=rays.device)
-            L.check(L.lib().ia_transform_rays_w2s(L.i64(n), C.c_void_p(rays.data_ptr()), L.i32(rays.stride(0)), L.ptr(w2s.detach().contiguous()), L.i32(0),
-                                                  L.ptr(out), L.stream()), "ia_transform_rays_w2s")
+            L.lib().ia_transform_rays_w2s(n, L.base_ptr(rays), rays.stride(0), w2s.detach().contiguous(), 0, out)
             return out
         rays_o = rays[:, :3] @ w2s[:3, :3].T + w2s[None, :3, 3]
         rays_d = rays[:, 3:6] @ w2s[:3, :3].T
@@ -220,30 +218,25 @@ class SNARFDeformer:
         IA_PACK=lookback: one pass with a chained scan, the packed list a prefix of x's storage (ia_deform_filter_compact)."""
         P, I = valid.shape
         dev = x.device
-        lib, st = L.lib(), L.stream()
         cnt = torch.empty(P, dtype=torch.int32, device=dev)
         start = torch.empty(P, dtype=torch.int32, device=dev)
         total = torch.empty(1, dtype=torch.int32, device=dev)
         src = torch.empty(P * I, dtype=torch.int32, device=dev) if with_src else None
         if os.environ.get("IA_PACK", "tiles") == "lookback":
-            nbytes = int(lib.ia_deform_filter_compact_tmp_bytes(L.i64(P)))
+            nbytes = int(L.lib().ia_deform_filter_compact_tmp_bytes(P))
             tmp = L.work_area(nbytes, dev)
-            L.check(lib.ia_deform_filter_compact(L.i64(P), L.i32(I), L.ptr(x), L.ptr(valid), L.ptr(cnt), L.ptr(start), L.ptr(x),
-                                                 L.ptr(src), L.ptr(None), L.ptr(total), L.ptr(tmp), C.c_size_t(nbytes), st),
-                    "ia_deform_filter_compact")
+            L.lib().ia_deform_filter_compact(P, I, x, valid, cnt, start, x, src, None, total, tmp, nbytes)
             Q = int(total.item())
             self._check_voxels()
             return x.reshape(-1, 3)[:Q], (src[:Q] if with_src else None), cnt, start, Q
-        nbytes = int(lib.ia_deform_filter_tiles_tmp_bytes(L.i64(P)))
+        nbytes = int(L.lib().ia_deform_filter_tiles_tmp_bytes(P))
         tmp = L.work_area(nbytes, dev)
-        L.check(lib.ia_deform_filter_tiles(L.i64(P), L.i32(I), L.ptr(x), L.ptr(valid), L.ptr(cnt), L.ptr(start), L.ptr(src), L.ptr(None),
-                                           L.ptr(total), L.ptr(tmp), C.c_size_t(nbytes), st), "ia_deform_filter_tiles")
+        L.lib().ia_deform_filter_tiles(P, I, x, valid, cnt, start, src, None, total, tmp, nbytes)
         Q = int(total.item())
         self._check_voxels()
         cand_x = torch.empty((Q, 3), device=dev)
         cand_src = torch.empty(Q, dtype=torch.int32, device=dev) if with_src else None
-        L.check(lib.ia_deform_pack_tiles(L.i64(P), L.i32(I), L.ptr(x), L.ptr(src), L.ptr(start), L.ptr(cand_x), L.ptr(cand_src),
-                                         L.ptr(tmp), st), "ia_deform_pack_tiles")
+        L.lib().ia_deform_pack_tiles(P, I, x, src, start, cand_x, cand_src, tmp)
         return cand_x, cand_src, cnt, start, Q
 
     SPEC_ROWS = os.environ.get("IA_BROYDEN_SPEC_ROWS", "1") == "1"
@@ -274,15 +267,14 @@ class SNARFDeformer:
             J_inv = r[3] if want_jinv else None
             res = self._normalized((*self._pack_candidates(x, valid, with_src=with_src), fwd, J_inv), normalize)
             return res + (None, None) if split else res
-        lib, st = L.lib(), L.stream()
         x_rows = torch.empty((P, 3, 3), device=dev)
         Jinv = torch.empty((1, P, I, 3, 3), device=dev) if want_jinv else None
         fwd = torch.empty((1, P, I, 3, 3), device=dev) if want_fwd else None
         cnt, meta, start, ovf_head = (torch.empty(P, dtype=torch.int32, device=dev) for _ in range(4))
         # overflow records + the list of points the kernel redoes with the filter off (1 / 64 of the batch): a grow-only work area
         # (locals, not attributes: concurrent calls on several streams -- render.compute_indirect_radiance -- each have their own)
-        ovf_scratch = L.work_area(lib.ia_spec_rows_overflow_bytes(L.i64(P)), dev, "spec_rows")
-        ovf_cap = self._tls.ovf_cap = int(lib.ia_spec_rows_overflow_capacity(L.i64(P)))
+        ovf_scratch = L.work_area(L.lib().ia_spec_rows_overflow_bytes(P), dev, "spec_rows")
+        ovf_cap = self._tls.ovf_cap = int(L.lib().ia_spec_rows_overflow_capacity(P))
         tot = torch.empty(2, dtype=torch.int32, device=dev)
         # IA_SEARCH_TOKEN=1 (experiment, measured without effect -- DESIGN 4.5): one search on the DEVICE at a time; this stream's search
         # starts when the previous search of any stream has finished, so that a search shares the device with another stream's gather /
@@ -325,17 +317,15 @@ class SNARFDeformer:
             tiles = (P + 1023) // 1024
             first_pos = torch.empty(P, dtype=torch.int32, device=dev)
             tile_off_n = torch.empty(tiles + 1, dtype=torch.int32, device=dev)         # [tiles] offsets + [1] n_first
-            L.check(lib.ia_deform_rows_pack_split(L.i64(P), L.i32(I), L.ptr(x_rows), L.ptr(cnt), L.ptr(meta), L.ptr(start), L.ptr(ovf_head),
-                                                  L.ptr(ovf_scratch), L.ptr(first_pos), L.ptr(tile_off_n), L.ptr(tile_off_n[tiles:]), L.ptr(cand_x),
-                                                  L.ptr(normalize[0].contiguous().float() if normalize else None),
-                                                  L.ptr(normalize[1].contiguous().float() if normalize else None),
-                                                  L.ptr(L.work_area(lib.ia_deform_rows_pack_split_tmp_bytes(L.i64(P)), dev)), st), "ia_deform_rows_pack_split")
+            L.lib().ia_deform_rows_pack_split(P, I, x_rows, cnt, meta, start, ovf_head, ovf_scratch, first_pos, tile_off_n, tile_off_n[tiles:],
+                                              cand_x, normalize[0].contiguous().float() if normalize else None,
+                                              normalize[1].contiguous().float() if normalize else None,
+                                              L.work_area(L.lib().ia_deform_rows_pack_split_tmp_bytes(P), dev))
             return cand_x, None, cnt, start, Q, None, None, (first_pos, tile_off_n[:tiles]), tile_off_n[tiles:]
         cand_src = torch.empty(Q, dtype=torch.int32, device=dev) if with_src else None
-        L.check(lib.ia_deform_rows_pack(L.i64(P), L.i32(I), L.ptr(x_rows), L.ptr(cnt), L.ptr(meta), L.ptr(start), L.ptr(ovf_head),
-                                        L.ptr(ovf_scratch), L.ptr(cand_x), L.ptr(cand_src),
-                                        L.ptr(normalize[0].contiguous().float() if normalize else None),
-                                        L.ptr(normalize[1].contiguous().float() if normalize else None), st), "ia_deform_rows_pack")
+        L.lib().ia_deform_rows_pack(P, I, x_rows, cnt, meta, start, ovf_head, ovf_scratch, cand_x, cand_src,
+                                    normalize[0].contiguous().float() if normalize else None,
+                                    normalize[1].contiguous().float() if normalize else None)
         res = (cand_x, cand_src, cnt, start, Q, (fwd[0] if want_fwd else None), (Jinv[0] if want_jinv else None))
         return res + (None, None) if split else res
 
@@ -417,20 +407,17 @@ class SNARFDeformer:
         pts = pts.contiguous().float()
         P, I = pts.shape[0], self.init_bones.shape[0]
         dev = self.device
-        lib, st = L.lib(), L.stream()
         # the candidates leave the packing kernel in the hash grid's coordinates (three elementwise passes over [Q,3] less)
         cand_x, _, cnt, start, Q, _, _, first_pos, n_first = self._candidates(pts, with_src=False, order=order,
                                                                              normalize=(geometry.center, geometry.scale), split=True)
         csdf = geometry.sdf_only(cand_x, normalized=True)
         sdf = torch.empty(P, device=dev)
         if first_pos is not None:     # split layout: first candidates at first_pos, the others from n_first on
-            L.check(lib.ia_deform_select_min_split(L.i64(P), L.ptr(start), L.ptr(cnt), L.ptr(first_pos[0]), L.ptr(first_pos[1]), L.ptr(n_first),
-                                                   L.ptr(csdf), L.ptr(order), L.ptr(sdf), st), "ia_deform_select_min_split")
+            L.lib().ia_deform_select_min_split(P, start, cnt, first_pos[0], first_pos[1], n_first, csdf, order, sdf)
         elif order is not None:         # pts = caller's points[order]: the result goes back to the caller's order on the way out
-            L.check(lib.ia_deform_select_min_scatter(L.i64(P), L.ptr(start), L.ptr(cnt), L.ptr(csdf), L.ptr(order), L.ptr(sdf), st),
-                    "ia_deform_select_min_scatter")
+            L.lib().ia_deform_select_min_scatter(P, start, cnt, csdf, order, sdf)
         else:
-            L.check(lib.ia_deform_select_min(L.i64(P), L.ptr(start), L.ptr(cnt), L.ptr(csdf), L.ptr(sdf), st), "ia_deform_select_min")
+            L.lib().ia_deform_select_min(P, start, cnt, csdf, sdf)
         return sdf
 
     @torch.no_grad()
@@ -441,7 +428,6 @@ class SNARFDeformer:
         pts = pts.contiguous().float()
         P, I = pts.shape[0], self.init_bones.shape[0]
         dev = self.device
-        lib, st = L.lib(), L.stream()
         cand_x, cand_src, cnt, start, Q, fwd, J_inv = self._candidates(pts, with_src=True, want_fwd=with_grad or want_fwd, want_jinv=want_jinv)
         # SDF network on the packed candidates
         cg = None
@@ -459,12 +445,8 @@ class SNARFDeformer:
             out["sdf_grad_cano"] = torch.empty((P, 3), device=dev)
         if with_feature:
             out["feature"] = torch.empty((P, 13), device=dev)
-        L.check(lib.ia_deform_select(
-            L.i64(P), L.ptr(start), L.ptr(cnt), L.ptr(cand_x), L.ptr(cand_src), L.ptr(csdf), L.i32(sdf_stride),
-            L.ptr(cg), L.ptr(cf if with_feature else None), L.i32(13), L.i32(13), L.ptr(fwd),
-            L.ptr(out["pts_cano"]), L.ptr(out["sdf"]), L.ptr(out["valid"]), L.ptr(out["sel"]),
-            L.ptr(out.get("sdf_grad")), L.ptr(out.get("sdf_grad_cano")), L.ptr(out.get("feature")), st),
-            "ia_deform_select")
+        L.lib().ia_deform_select(P, start, cnt, cand_x, cand_src, csdf, sdf_stride, cg, cf if with_feature else None, 13, 13, fwd, out["pts_cano"],
+                                 out["sdf"], out["valid"], out["sel"], out.get("sdf_grad"), out.get("sdf_grad_cano"), out.get("feature"))
         return out
 
 

@@ -36,9 +36,7 @@ def precompute(voxel_w: Tensor, tfs: Tensor, voxel_d: Tensor, voxel_J: Tensor, o
     for t in (voxel_d, voxel_J, voxel_J_cl):
         if t is not None and (not t.is_contiguous() or t.dtype != torch.float32):
             raise RuntimeError("output grids must be contiguous float32")
-    L.check(L.lib().ia_precompute(L.i32(B), L.i32(D), L.i32(H), L.i32(W), L.ptr(voxel_w), L.ptr(tfs), L.ptr(off),
-                                  L.ptr(sc), L.ptr(voxel_d), L.ptr(voxel_J), L.ptr(voxel_J_cl), L.stream()),
-            "ia_precompute")
+    L.lib().ia_precompute(B, D, H, W, voxel_w, tfs, off, sc, voxel_d, voxel_J, voxel_J_cl)
 
 
 CELL_TAU = 2.5        # a voxel cell is tight when |(dg/dx)^-1|_F <= CELL_TAU all over it (a rotation has sqrt(3) = 1.73)
@@ -53,8 +51,7 @@ def cell_tightness(voxel_J: ChannelLastVoxelJ, offset: Tensor, scale: Tensor, ta
     assert isinstance(voxel_J, ChannelLastVoxelJ) and voxel_J.data.shape[0] == 1
     _, D, H, W, _ = voxel_J.data.shape
     out = torch.empty((D, H, W), dtype=torch.uint8, device=voxel_J.data.device)
-    L.check(L.lib().ia_cell_tightness(L.i32(D), L.i32(H), L.i32(W), L.ptr(voxel_J.data), L.ptr(offset.reshape(3).contiguous().float()),
-                                      L.ptr(scale.reshape(3).contiguous().float()), L.f32(tau), L.ptr(out), L.stream()), "ia_cell_tightness")
+    L.lib().ia_cell_tightness(D, H, W, voxel_J.data, offset.reshape(3).contiguous().float(), scale.reshape(3).contiguous().float(), tau, out)
     return out
 
 
@@ -89,10 +86,7 @@ def fuse_broyden(x: Tensor, xd_tgt: Tensor, voxel: Tensor, voxel_J, tfs: Tensor,
     tfs = tfs.contiguous().float()
     bones = bone_ids.contiguous().to(torch.int32)
     off, sc = offset.reshape(3).contiguous().float(), scale.reshape(3).contiguous().float()
-    L.check(L.lib().ia_fuse_broyden(L.i32(B), L.i64(N), L.i32(I), L.ptr(xd), L.ptr(vj), L.i32(layout), L.i32(D),
-                                    L.i32(H), L.i32(W), L.ptr(tfs), L.ptr(bones), L.ptr(off), L.ptr(sc),
-                                    L.f32(cvg_threshold), L.f32(dvg_threshold), L.ptr(x), L.ptr(J_inv),
-                                    L.ptr(is_valid), L.ptr(fwd_J), L.stream()), "ia_fuse_broyden")
+    L.lib().ia_fuse_broyden(B, N, I, xd, vj, layout, D, H, W, tfs, bones, off, sc, cvg_threshold, dvg_threshold, x, J_inv, is_valid, fwd_J)
 
 
 def fuse_broyden_spec(x: Tensor, xd_tgt: Tensor, voxel_J: ChannelLastVoxelJ, tfs: Tensor, bone_ids: Tensor, J_inv: Tensor,
@@ -115,11 +109,9 @@ def fuse_broyden_spec(x: Tensor, xd_tgt: Tensor, voxel_J: ChannelLastVoxelJ, tfs
     for t in (x, J_inv, is_valid, fwd_J):
         if t is not None and not t.is_contiguous():
             raise RuntimeError("outputs must be contiguous")
-    L.check(L.lib().ia_fuse_broyden_spec(
-        L.i64(N), L.i32(I), L.ptr(xd_tgt.contiguous().float()), L.ptr(voxel_J.data), L.i32(D), L.i32(H), L.i32(W),
-        L.ptr(tfs.contiguous().float()), L.ptr(bone_ids.contiguous().to(torch.int32)), L.ptr(offset.reshape(3).contiguous().float()),
-        L.ptr(scale.reshape(3).contiguous().float()), L.f32(cvg_threshold), L.f32(dvg_threshold), L.f32(eps), L.ptr(x), L.ptr(J_inv),
-        L.ptr(is_valid), L.ptr(fwd_J), L.ptr(counters), L.ptr(_cell_tight_arg(cell_tight, voxel_J)), L.stream()), "ia_fuse_broyden_spec")
+    L.lib().ia_fuse_broyden_spec(N, I, xd_tgt.contiguous().float(), voxel_J.data, D, H, W, tfs.contiguous().float(),
+                                 bone_ids.contiguous().to(torch.int32), offset.reshape(3).contiguous().float(), scale.reshape(3).contiguous().float(),
+                                 cvg_threshold, dvg_threshold, eps, x, J_inv, is_valid, fwd_J, counters, _cell_tight_arg(cell_tight, voxel_J))
 
 
 def fuse_broyden_spec_rows(x_rows: Tensor, xd_tgt: Tensor, voxel_J: ChannelLastVoxelJ, tfs: Tensor, bone_ids: Tensor, J_inv: Tensor,
@@ -143,20 +135,18 @@ def fuse_broyden_spec_rows(x_rows: Tensor, xd_tgt: Tensor, voxel_J: ChannelLastV
     assert x_rows.shape == (N, 3, 3) and all(t.shape == (N,) and t.dtype == torch.int32 for t in (cnt, meta, start, ovf_head))
     assert total_and_overflow.shape == (2,) and total_and_overflow.dtype == torch.int32
     # the work area grows with N (flagged list of max(65536, N / 64) entries): a caller's buffer sized for another N would be overrun
-    need = int(L.lib().ia_spec_rows_overflow_bytes(L.i64(N)))
+    need = int(L.lib().ia_spec_rows_overflow_bytes(N))
     if ovf_scratch.dtype != torch.uint8 or not ovf_scratch.is_contiguous() or ovf_scratch.numel() < need:
         raise RuntimeError(f"ovf_scratch must be a contiguous uint8 tensor of at least ia_spec_rows_overflow_bytes(N={N}) = {need} bytes "
                            f"(got {ovf_scratch.dtype}, {ovf_scratch.numel()})")
     for t in (x_rows, J_inv, fwd_J, cnt, meta, start):
         if t is not None and not t.is_contiguous():
             raise RuntimeError("outputs must be contiguous")
-    L.check(L.lib().ia_fuse_broyden_spec_rows(
-        L.i64(N), L.i32(I), L.ptr(xd_tgt.contiguous().float()), L.ptr(voxel_J.data), L.i32(D), L.i32(H), L.i32(W),
-        L.ptr(tfs.contiguous().float()), L.ptr(bone_ids.contiguous().to(torch.int32)), L.ptr(offset.reshape(3).contiguous().float()),
-        L.ptr(scale.reshape(3).contiguous().float()), L.f32(cvg_threshold), L.f32(dvg_threshold), L.f32(eps), L.ptr(x_rows), L.ptr(J_inv),
-        L.ptr(fwd_J), L.ptr(cnt), L.ptr(meta), L.ptr(start), L.ptr(ovf_head), L.ptr(ovf_scratch), L.ptr(total_and_overflow),
-        L.ptr(L.scan_tmp(N, xd_tgt.device)), L.ptr(counters), L.ptr(order), L.ptr(_cell_tight_arg(cell_tight, voxel_J)), L.stream()),
-        "ia_fuse_broyden_spec_rows")
+    L.lib().ia_fuse_broyden_spec_rows(N, I, xd_tgt.contiguous().float(), voxel_J.data, D, H, W, tfs.contiguous().float(),
+                                      bone_ids.contiguous().to(torch.int32), offset.reshape(3).contiguous().float(),
+                                      scale.reshape(3).contiguous().float(), cvg_threshold, dvg_threshold, eps, x_rows, J_inv, fwd_J, cnt, meta,
+                                      start, ovf_head, ovf_scratch, total_and_overflow, L.scan_tmp(N, xd_tgt.device), counters, order,
+                                      _cell_tight_arg(cell_tight, voxel_J))
 
 
 def filter(x: Tensor, mask: Tensor) -> Tensor:
@@ -168,7 +158,7 @@ def filter(x: Tensor, mask: Tensor) -> Tensor:
     x = x.contiguous().float()
     mask = mask.contiguous()
     out = torch.empty_like(mask)
-    L.check(L.lib().ia_filter(L.i64(N), L.i32(I), L.ptr(x), L.ptr(mask), L.ptr(out), L.stream()), "ia_filter")
+    L.lib().ia_filter(N, I, x, mask, out)
     return out
 
 
@@ -196,10 +186,8 @@ def forward_skinning(xc: Tensor, voxel_w: Tensor, tfs: Tensor, offset: Tensor, s
     w = torch.empty((P, 24), dtype=torch.float32, device=dev) if want_weights else None
     xd = torch.empty((P, 3), dtype=torch.float32, device=dev) if want_xd else None
     R = torch.empty((P, 3, 3), dtype=torch.float32, device=dev) if want_rot else None
-    L.check(L.lib().ia_forward_skinning(L.i64(P), L.ptr(xc), L.ptr(voxel_w.detach().contiguous().float()), L.i32(D), L.i32(H), L.i32(W),
-                                        L.ptr(offset.detach().reshape(3).contiguous().float()),
-                                        L.ptr(scale.detach().reshape(3).contiguous().float()), L.ptr(tfs), L.ptr(w), L.ptr(xd), L.ptr(R),
-                                        L.stream()), "ia_forward_skinning")
+    L.lib().ia_forward_skinning(P, xc, voxel_w.detach().contiguous().float(), D, H, W, offset.detach().reshape(3).contiguous().float(),
+                                scale.detach().reshape(3).contiguous().float(), tfs, w, xd, R)
     return xd, R, w
 
 
@@ -212,8 +200,7 @@ def skin_grid_points(D: int, H: int, W: int, ratio: float, scale: float, offset,
     """voxel centres [D*H*W,3] of switch_to_explicit (deformer_torch.py:145-186): linspace(-1, 1) per axis, z / ratio, * scale, + offset."""
     out = torch.empty((D * H * W, 3), dtype=torch.float32, device=device)
     ox, oy, oz = (float(v) for v in offset)
-    L.check(L.lib().ia_skin_grid_points(L.i32(D), L.i32(H), L.i32(W), L.f32(ratio), L.f32(scale), L.f32(ox), L.f32(oy), L.f32(oz),
-                                        L.ptr(out), L.stream()), "ia_skin_grid_points")
+    L.lib().ia_skin_grid_points(D, H, W, ratio, scale, ox, oy, oz, out)
     return out
 
 
@@ -223,8 +210,7 @@ def skin_blend(d2: Tensor, idx: Tensor, weights: Tensor) -> Tensor:
     if idx.dtype != torch.int32 or idx.shape != d2.shape or weights.dim() != 2 or weights.shape[1] != 24:
         raise RuntimeError("skin_blend: d2 [P,K] fp32, idx [P,K] int32, weights [V,24]")
     out = torch.empty((24, P), dtype=torch.float32, device=d2.device)
-    L.check(L.lib().ia_skin_blend(L.i64(P), L.i32(weights.shape[0]), L.i32(K), L.ptr(d2.contiguous().float()), L.ptr(idx.contiguous()),
-                                  L.ptr(weights.contiguous().float()), L.ptr(out), L.stream()), "ia_skin_blend")
+    L.lib().ia_skin_blend(P, weights.shape[0], K, d2.contiguous().float(), idx.contiguous(), weights.contiguous().float(), out)
     return out
 
 
@@ -240,7 +226,7 @@ def skin_smooth(weights: Tensor, sweeps: int = SMOOTH_SWEEPS) -> Tensor:
         a = a.clone()                                    # the caller's tensor is not written
     b = torch.empty_like(a)
     for _ in range(sweeps):
-        L.check(L.lib().ia_skin_smooth(L.i32(D), L.i32(H), L.i32(W), L.ptr(a), L.ptr(b), L.stream()), "ia_skin_smooth")
+        L.lib().ia_skin_smooth(D, H, W, a, b)
         a, b = b, a
     return a
 

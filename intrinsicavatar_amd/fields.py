@@ -29,9 +29,7 @@ HASH = dict(n_levels=16, n_features_per_level=2, log2_hashmap_size=19, base_reso
 
 
 def hash_n_entries(cfg=HASH) -> int:
-    lib = L.lib()
-    return int(lib.ia_hashgrid_n_entries(L.i32(cfg["n_levels"]), L.i32(cfg["log2_hashmap_size"]),
-                                         L.i32(cfg["base_resolution"]), L.f32(cfg["per_level_scale"])))
+    return int(L.lib().ia_hashgrid_n_entries(cfg["n_levels"], cfg["log2_hashmap_size"], cfg["base_resolution"], cfg["per_level_scale"]))
 
 
 def hashgrid_forward(x01: Tensor, params: Tensor, cfg=HASH, with_jac: bool = False, out: Optional[Tensor] = None):
@@ -48,17 +46,13 @@ def hashgrid_forward(x01: Tensor, params: Tensor, cfg=HASH, with_jac: bool = Fal
     # call in 2.72 ms against 3.29 ms, so the Jacobian call stays flat
     method = os.environ.get("IA_HASH_FWD") or ("xcd" if (n >= HASH_FWD_XCD_MIN and not with_jac) else "flat")
     if method == "xcd":
-        nb = int(L.lib().ia_hashgrid_fwd_scratch_bytes(L.i64(n), L.i32(cfg["n_levels"]), L.i32(1 if with_jac else 0)))
+        nb = int(L.lib().ia_hashgrid_fwd_scratch_bytes(n, cfg["n_levels"], 1 if with_jac else 0))
         scratch = L.work_area(nb, x01.device)
-        L.check(L.lib().ia_hashgrid_fwd_xcd(L.i64(n), L.ptr(x01), L.ptr(params), L.i32(cfg["n_levels"]),
-                                            L.i32(cfg["n_features_per_level"]), L.i32(cfg["log2_hashmap_size"]),
-                                            L.i32(cfg["base_resolution"]), L.f32(cfg["per_level_scale"]), L.ptr(out),
-                                            L.i32(out.stride(0)), L.ptr(jac), L.ptr(scratch), L.stream()), "ia_hashgrid_fwd_xcd")
+        L.lib().ia_hashgrid_fwd_xcd(n, x01, params, cfg["n_levels"], cfg["n_features_per_level"], cfg["log2_hashmap_size"], cfg["base_resolution"],
+                                    cfg["per_level_scale"], out, out.stride(0), jac, scratch)
         return (out, jac) if with_jac else out
-    L.check(L.lib().ia_hashgrid_fwd(L.i64(n), L.ptr(x01), L.ptr(params), L.i32(cfg["n_levels"]),
-                                    L.i32(cfg["n_features_per_level"]), L.i32(cfg["log2_hashmap_size"]),
-                                    L.i32(cfg["base_resolution"]), L.f32(cfg["per_level_scale"]), L.ptr(out),
-                                    L.i32(out.stride(0)), L.ptr(jac), L.stream()), "ia_hashgrid_fwd")
+    L.lib().ia_hashgrid_fwd(n, x01, params, cfg["n_levels"], cfg["n_features_per_level"], cfg["log2_hashmap_size"], cfg["base_resolution"],
+                            cfg["per_level_scale"], out, out.stride(0), jac)
     return (out, jac) if with_jac else out
 
 
@@ -74,26 +68,19 @@ def hashgrid_backward(x01: Tensor, g_enc: Optional[Tensor], grad_params: Tensor,
     method: None (by batch size; env IA_HASH_BWD overrides) | 'atomic' | 'binned'."""
     n = x01.shape[0]
     method = method or os.environ.get("IA_HASH_BWD") or ("binned" if n >= HASH_BWD_BINNED_MIN else "atomic")
-    cargs = (L.i32(cfg["n_levels"]), L.i32(cfg["n_features_per_level"]), L.i32(cfg["log2_hashmap_size"]),
-             L.i32(cfg["base_resolution"]), L.f32(cfg["per_level_scale"]))
+    cargs = (cfg["n_levels"], cfg["n_features_per_level"], cfg["log2_hashmap_size"], cfg["base_resolution"], cfg["per_level_scale"])
     if method == "atomic":
-        L.check(L.lib().ia_hashgrid_bwd(L.i64(n), L.ptr(x01), *cargs, L.ptr(g_enc),
-                                        L.i32(g_enc.stride(0) if g_enc is not None else 0), L.ptr(g_jac),
-                                        L.i32(g_jac.stride(0) if g_jac is not None else 0), L.ptr(q), L.ptr(grad_params),
-                                        L.stream()), "ia_hashgrid_bwd")
+        L.lib().ia_hashgrid_bwd(n, x01, *cargs, g_enc, g_enc.stride(0) if g_enc is not None else 0, g_jac,
+                                g_jac.stride(0) if g_jac is not None else 0, q, grad_params)
         return
     for c0 in range(0, n, HASH_BWD_CHUNK):
         m = min(HASH_BWD_CHUNK, n - c0)
-        nb = int(L.lib().ia_hashgrid_bwd_scratch_bytes(L.i64(m), L.i32(cfg["n_levels"]), L.i32(cfg["log2_hashmap_size"]),
-                                                       L.i32(cfg["base_resolution"]), L.f32(cfg["per_level_scale"])))
+        nb = int(L.lib().ia_hashgrid_bwd_scratch_bytes(m, cfg["n_levels"], cfg["log2_hashmap_size"], cfg["base_resolution"], cfg["per_level_scale"]))
         scratch = L.work_area(nb, x01.device)
         sl = lambda t: None if t is None else t[c0:c0 + m]      # noqa: E731  (row slices keep stride / contiguity)
         ge, gj = sl(g_enc), sl(g_jac)
-        L.check(L.lib().ia_hashgrid_bwd_binned(
-            L.i64(m), L.ptr(sl(x01)), *cargs, L.ptr(ge), L.i32(ge.stride(0) if ge is not None else 0), L.ptr(gj),
-            L.i32(gj.stride(0) if gj is not None else 0), L.ptr(sl(q)), L.ptr(grad_params), C.c_uint32(level_mask & 0xFFFFFFFF),
-            L.ptr(scratch), L.i64(nb),
-            L.stream()), "ia_hashgrid_bwd_binned")
+        L.lib().ia_hashgrid_bwd_binned(m, sl(x01), *cargs, ge, ge.stride(0) if ge is not None else 0, gj, gj.stride(0) if gj is not None else 0,
+                                       sl(q), grad_params, level_mask & 0xFFFFFFFF, scratch, nb)
 
 
 def sh4(d01: Tensor, out: Optional[Tensor] = None) -> Tensor:
@@ -101,7 +88,7 @@ def sh4(d01: Tensor, out: Optional[Tensor] = None) -> Tensor:
     d01 = d01.contiguous().float()
     if out is None:
         out = torch.empty((n, 16), dtype=torch.float32, device=d01.device)
-    L.check(L.lib().ia_sh4_fwd(L.i64(n), L.ptr(d01), L.ptr(out), L.i32(out.stride(0)), L.stream()), "ia_sh4_fwd")
+    L.lib().ia_sh4_fwd(n, d01, out, out.stride(0))
     return out
 
 
@@ -110,30 +97,13 @@ def mlp_forward(kind: int, segs, W1, b1, W2, b2, Wo, bo, out_dim: int, jac=None,
     """segs: list of (tensor [n,w_total>=w], width, mul, add). Returns y [n,out_dim] (+ grad [n,3])."""
     n = segs[0][0].shape[0]
     dev = segs[0][0].device
-    ns = len(segs)
-    keep = []
-    ptrs = (C.c_void_p * ns)()
-    strides = (C.c_int * ns)()
-    widths = (C.c_int * ns)()
-    muls = (C.c_float * ns)()
-    adds = (C.c_float * ns)()
-    for i, (t, w, m, a) in enumerate(segs):
-        if t.stride(-1) != 1 or t.dtype != torch.float32 or not t.is_cuda:
-            raise L.IaError("MLP input segments must be float32 GPU tensors with unit inner stride")
-        keep.append(t)
-        ptrs[i] = t.data_ptr()
-        strides[i] = t.stride(0)
-        widths[i] = w
-        muls[i] = m
-        adds[i] = a
+    ns, ptrs, strides, widths, muls, adds = L.segments(segs)
     y = torch.empty((n, out_dim), dtype=torch.float32, device=dev)
     grad = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_grad else None
     inv = (C.c_float * 3)(*[float(v) for v in inv_scale]) if inv_scale is not None else None
     cont = [t.contiguous().float() if t is not None else None for t in (W1, b1, W2, b2, Wo, bo)]
-    L.check(L.lib().ia_mlp_fwd(L.i32(kind), L.i64(n), L.i32(ns), ptrs, strides, widths, muls, adds,
-                               L.ptr(cont[0]), L.ptr(cont[1]), L.ptr(cont[2]), L.ptr(cont[3]), L.ptr(cont[4]),
-                               L.ptr(cont[5]), L.ptr(y), L.i32(out_dim), L.ptr(jac), L.i32(xyz_col), inv, L.ptr(grad),
-                               L.stream()), "ia_mlp_fwd")
+    L.lib().ia_mlp_fwd(kind, n, ns, ptrs, strides, widths, muls, adds, cont[0], cont[1], cont[2], cont[3], cont[4], cont[5], y, out_dim, jac, xyz_col,
+                       inv, grad)
     return (y, grad) if want_grad else y
 
 
@@ -179,7 +149,7 @@ def normalize_points(x: Tensor, center: Tensor, scale: Tensor) -> Tensor:
     """(x - center) / scale + 0.5 in one launch (ia_normalize_points): the [0,1]^3 coordinates of a hash grid."""
     x = x.contiguous().float()
     out = torch.empty_like(x)
-    L.check(L.lib().ia_normalize_points(L.i64(x.shape[0]), L.ptr(x), L.ptr(center), L.ptr(scale), L.ptr(out), L.stream()), "ia_normalize_points")
+    L.lib().ia_normalize_points(x.shape[0], x, center, scale, out)
     return out
 
 
@@ -193,8 +163,7 @@ class _EffW(torch.autograd.Function):
         gg = g.contiguous() if g is not None else None
         M, N = v.shape
         out = torch.empty((M, N), device=v.device)
-        L.check(L.lib().ia_effective_weights(L.i32(mode), L.i32(M), L.i32(N), L.ptr(gg), L.ptr(v), L.ptr(src), L.ptr(mul), L.ptr(out), L.stream()),
-                "ia_effective_weights")
+        L.lib().ia_effective_weights(mode, M, N, gg, v, src, mul, out)
         ctx.mode = mode
         ctx.save_for_backward(gg, v, src, mul)
         return out
@@ -205,8 +174,7 @@ class _EffW(torch.autograd.Function):
         M, N = v.shape
         g_v = torch.empty_like(v)
         g_g = torch.empty_like(gg) if gg is not None else None
-        L.check(L.lib().ia_effective_weights_bwd(L.i32(ctx.mode), L.i32(M), L.i32(N), L.ptr(gg), L.ptr(v), L.ptr(src), L.ptr(mul),
-                                                 L.ptr(g_out.contiguous()), L.ptr(g_v), L.ptr(g_g), L.stream()), "ia_effective_weights_bwd")
+        L.lib().ia_effective_weights_bwd(ctx.mode, M, N, gg, v, src, mul, g_out.contiguous(), g_v, g_g)
         return None, g_g, g_v, None, None
 
 
@@ -368,16 +336,13 @@ class VolumeSDF(nn.Module):
             return self.forward(points, with_grad=False, with_feature=False).contiguous()
         cfg = HASH
         xp = points.contiguous() if normalized else normalize_points(points, self.center, self.scale)
-        nb = int(L.lib().ia_hashgrid_fwd_scratch_bytes(L.i64(n), L.i32(cfg["n_levels"]), L.i32(0)))
+        nb = int(L.lib().ia_hashgrid_fwd_scratch_bytes(n, cfg["n_levels"], 0))
         scratch = L.work_area(nb, xp.device, "hash_levels")
-        L.check(L.lib().ia_hashgrid_fwd_xcd(L.i64(n), L.ptr(xp), L.ptr(self.grid_params), L.i32(cfg["n_levels"]),
-                                            L.i32(cfg["n_features_per_level"]), L.i32(cfg["log2_hashmap_size"]),
-                                            L.i32(cfg["base_resolution"]), L.f32(cfg["per_level_scale"]), L.ptr(None), L.i32(0),
-                                            L.ptr(None), L.ptr(scratch), L.stream()), "ia_hashgrid_fwd_xcd")
+        L.lib().ia_hashgrid_fwd_xcd(n, xp, self.grid_params, cfg["n_levels"], cfg["n_features_per_level"], cfg["log2_hashmap_size"],
+                                    cfg["base_resolution"], cfg["per_level_scale"], None, 0, None, scratch)
         W1k, b1, W2, b2 = self.effective_weights()
         sdf = torch.empty(n, device=xp.device)
-        L.check(L.lib().ia_sdf_levels_fwd(L.i64(n), L.ptr(scratch), L.ptr(xp), L.ptr(W1k.contiguous()), L.ptr(b1.contiguous()),
-                                          L.ptr(W2.contiguous()), L.ptr(b2.contiguous()), L.ptr(sdf), L.stream()), "ia_sdf_levels_fwd")
+        L.lib().ia_sdf_levels_fwd(n, scratch, xp, W1k.contiguous(), b1.contiguous(), W2.contiguous(), b2.contiguous(), sdf)
         return sdf
 
     @torch.no_grad()
@@ -396,21 +361,17 @@ class VolumeSDF(nn.Module):
             # big batches: one-table-at-a-time gather with Jacobian, level-major results straight into the head (no [n,32] rows, no
             # [n,32,3] Jacobian tensor, coalesced Jacobian reads in the gradient epilogue)
             cfg = HASH
-            lib, st = L.lib(), L.stream()
-            nb = int(lib.ia_hashgrid_fwd_scratch_bytes(L.i64(n), L.i32(cfg["n_levels"]), L.i32(1)))
+            nb = int(L.lib().ia_hashgrid_fwd_scratch_bytes(n, cfg["n_levels"], 1))
             scratch = L.work_area(nb, xp.device, "hash_levels_jac")
-            L.check(lib.ia_hashgrid_fwd_levels(L.i64(n), L.ptr(xp), L.ptr(self.grid_params), L.i32(cfg["n_levels"]),
-                                               L.i32(cfg["n_features_per_level"]), L.i32(cfg["log2_hashmap_size"]),
-                                               L.i32(cfg["base_resolution"]), L.f32(cfg["per_level_scale"]), L.i32(1), L.ptr(scratch), st),
-                    "ia_hashgrid_fwd_levels")
-            joff = int(lib.ia_hashgrid_fwd_levels_jac_offset(L.i64(n), L.i32(cfg["n_levels"])))
+            L.lib().ia_hashgrid_fwd_levels(n, xp, self.grid_params, cfg["n_levels"], cfg["n_features_per_level"], cfg["log2_hashmap_size"],
+                                           cfg["base_resolution"], cfg["per_level_scale"], 1, scratch)
+            joff = int(L.lib().ia_hashgrid_fwd_levels_jac_offset(n, cfg["n_levels"]))
             W1k, b1, W2, b2 = self.effective_weights()
             y = torch.empty((n, 13), device=xp.device)
             grad = torch.empty((n, 3), device=xp.device)
             inv = (C.c_float * 3)(*[float(v) for v in self.inv_scale_host()])
-            L.check(lib.ia_sdf_levels_fwd_grad(L.i64(n), L.ptr(scratch), C.c_void_p(scratch.data_ptr() + joff), L.ptr(xp),
-                                               L.ptr(W1k.contiguous()), L.ptr(b1.contiguous()), L.ptr(W2.contiguous()), L.ptr(b2.contiguous()),
-                                               L.ptr(y), L.i32(13), inv, L.ptr(grad), st), "ia_sdf_levels_fwd_grad")
+            L.lib().ia_sdf_levels_fwd_grad(n, scratch, scratch[joff:], xp, W1k.contiguous(), b1.contiguous(), W2.contiguous(),
+                                           b2.contiguous(), y, 13, inv, grad)
             out = [y[:, 0], grad]
             if with_feature:
                 out.append(y)
@@ -630,8 +591,7 @@ class _GaussianHistogram(torch.autograd.Function):
         x = x.detach().reshape(-1).float().contiguous()
         sg = sigma.detach().reshape(1).float().contiguous()
         out = torch.zeros(bins, device=x.device)
-        L.check(L.lib().ia_gaussian_histogram(L.i64(x.shape[0]), L.ptr(x), L.ptr(sg), L.i32(bins), L.f32(vmin), L.f32(vmax), L.ptr(out),
-                                              L.stream()), "ia_gaussian_histogram")
+        L.lib().ia_gaussian_histogram(x.shape[0], x, sg, bins, vmin, vmax, out)
         ctx.cfg = (bins, vmin, vmax)
         ctx.save_for_backward(x, sg)
         return out
@@ -641,9 +601,7 @@ class _GaussianHistogram(torch.autograd.Function):
         x, sg = ctx.saved_tensors
         bins, vmin, vmax = ctx.cfg
         gx, gs = torch.empty_like(x), torch.zeros(1, device=x.device)
-        L.check(L.lib().ia_gaussian_histogram_bwd(L.i64(x.shape[0]), L.ptr(x), L.ptr(sg), L.i32(bins), L.f32(vmin), L.f32(vmax),
-                                                  L.ptr(g.float().contiguous()), L.ptr(gx), L.ptr(gs), L.stream()),
-                "ia_gaussian_histogram_bwd")
+        L.lib().ia_gaussian_histogram_bwd(x.shape[0], x, sg, bins, vmin, vmax, g.float().contiguous(), gx, gs)
         return gx, gs.reshape(()), None, None, None
 
 

@@ -28,10 +28,8 @@ def _resample_info(packed_info: Tensor, n: int, add_steps: bool, read_total: boo
     dev = packed_info.device
     rpi = torch.empty((n_rays, 2), dtype=torch.int32, device=dev)
     total = torch.empty(1, dtype=torch.int32, device=dev)          # written by the scan
-    tmp = L.work_area(L.lib().ia_pack_info_tmp_bytes(L.i64(n_rays)), dev)
-    L.check(L.lib().ia_resample_packed_info(L.i64(n_rays), L.ptr(packed_info), L.i32(n), L.i32(int(add_steps)),
-                                            L.ptr(rpi), L.ptr(total), L.ptr(tmp), L.stream()),
-            "ia_resample_packed_info")
+    tmp = L.work_area(L.lib().ia_pack_info_tmp_bytes(n_rays), dev)
+    L.lib().ia_resample_packed_info(n_rays, packed_info, n, int(add_steps), rpi, total, tmp)
     if not read_total:
         return rpi, n * n_rays
     return rpi, int(total.item())     # the .item() of cdf.cu:183
@@ -43,7 +41,7 @@ def _f32v(t: Tensor, n: Optional[int] = None) -> Tensor:
 
 def _resample_tmp(n_rays: int, n_in: int, n: int, dev) -> Tensor:
     """scratch of one K1..K4 call: u-table, CDF tables, per-ray records (csrc/resample.hip)."""
-    return L.work_area(L.lib().ia_resample_tmp_bytes(L.i64(n_rays), L.i64(n_in), L.i32(n)), dev)
+    return L.work_area(L.lib().ia_resample_tmp_bytes(n_rays, n_in, n), dev)
 
 
 # ----------------------------------------------------------------------------- K1
@@ -68,9 +66,7 @@ def ray_resampling(packed_info: Tensor, t_starts: Tensor, t_ends: Tensor, weight
     fg = torch.empty((w.shape[0],), dtype=torch.int32, device=dev)
     bg = torch.empty((n_rays,), dtype=torch.int32, device=dev)
     tmp = _resample_tmp(n_rays, w.shape[0], n_samples, dev)
-    L.check(L.lib().ia_ray_resampling(L.i64(n_rays), L.i64(w.shape[0]), L.i32(n_samples), L.ptr(packed_info), L.ptr(st), L.ptr(en),
-                                      L.ptr(w), L.ptr(sd), L.ptr(rpi), L.i64(T), L.ptr(ts), L.ptr(offs), L.ptr(surface_idx), L.ptr(idxs),
-                                      L.ptr(fg), L.ptr(bg), L.ptr(tmp), L.stream()), "ia_ray_resampling")
+    L.lib().ia_ray_resampling(n_rays, w.shape[0], n_samples, packed_info, st, en, w, sd, rpi, T, ts, offs, surface_idx, idxs, fg, bg, tmp)
     return rpi, ts, offs, idxs, fg, bg, surface_idx
 
 
@@ -89,8 +85,7 @@ def ray_resampling_capacity(packed_info: Tensor, t_starts: Tensor, t_ends: Tenso
     cap = int(n_samples) * n_rays
     assert cap < (1 << 31), "n_samples x n_rays must stay below 2^31"
     rpi = torch.empty((n_rays, 2), dtype=torch.int32, device=dev)
-    L.check(L.lib().ia_resample_packed_info(L.i64(n_rays), L.ptr(packed_info), L.i32(n_samples), L.i32(0), L.ptr(rpi), L.ptr(total),
-                                            L.ptr(L.work_area(L.lib().ia_pack_info_tmp_bytes(L.i64(n_rays)), dev)), L.stream()), "ia_resample_packed_info")
+    L.lib().ia_resample_packed_info(n_rays, packed_info, n_samples, 0, rpi, total, L.work_area(L.lib().ia_pack_info_tmp_bytes(n_rays), dev))
     ts = torch.empty((cap, 1), dtype=torch.float32, device=dev)
     offs = torch.empty((cap, 1), dtype=torch.float32, device=dev)
     idxs = torch.empty((cap,), dtype=torch.int64, device=dev)
@@ -98,9 +93,8 @@ def ray_resampling_capacity(packed_info: Tensor, t_starts: Tensor, t_ends: Tenso
     fg = torch.empty((w.shape[0],), dtype=torch.int32, device=dev)
     bg = torch.empty((n_rays,), dtype=torch.int32, device=dev)
     tmp = _resample_tmp(n_rays, w.shape[0], n_samples, dev)
-    L.check(L.lib().ia_ray_resampling_upto(L.i64(n_rays), L.i64(w.shape[0]), L.i32(n_samples), L.ptr(packed_info), L.ptr(st), L.ptr(en),
-                                           L.ptr(w), L.ptr(sd), L.ptr(rpi), L.i64(cap), L.ptr(total), L.ptr(ts), L.ptr(offs),
-                                           L.ptr(surface_idx), L.ptr(idxs), L.ptr(fg), L.ptr(bg), L.ptr(tmp), L.stream()), "ia_ray_resampling_upto")
+    L.lib().ia_ray_resampling_upto(n_rays, w.shape[0], n_samples, packed_info, st, en, w, sd, rpi, cap, total, ts, offs, surface_idx, idxs, fg, bg,
+                                   tmp)
     return rpi, ts, offs, idxs, fg, bg, surface_idx
 
 
@@ -122,9 +116,7 @@ def ray_resampling_merge(packed_info: Tensor, vals: Tensor, is_left: Tensor, is_
     f = torch.empty((2, T), dtype=torch.float32, device=dev)
     b = torch.empty((4, T), dtype=torch.bool, device=dev)
     tmp = _resample_tmp(n_rays, vals.shape[0], n_samples, dev)
-    L.check(L.lib().ia_ray_resampling_merge(L.i64(n_rays), L.i64(vals.shape[0]), L.i32(n_samples), L.ptr(packed_info), L.ptr(vals),
-                                            L.ptr(il), L.ptr(ir), L.ptr(w), L.ptr(rpi), L.ptr(f[0]), L.ptr(f[1]), L.ptr(b[0]), L.ptr(b[1]),
-                                            L.ptr(b[2]), L.ptr(b[3]), L.ptr(tmp), L.stream()), "ia_ray_resampling_merge")
+    L.lib().ia_ray_resampling_merge(n_rays, vals.shape[0], n_samples, packed_info, vals, il, ir, w, rpi, f[0], f[1], b[0], b[1], b[2], b[3], tmp)
     # (resampled_packed_info, vals, dists, is_left, is_right, is_resampled, is_fg_sample)
     return rpi, f[0], f[1], b[0], b[1], b[2], b[3]
 
@@ -142,21 +134,17 @@ def ray_resampling_merge_compact(packed_info: Tensor, vals: Tensor, is_left: Ten
     if il.dtype != torch.bool or ir.dtype != torch.bool:
         raise RuntimeError("is_left/is_right must be bool")
     n_rays, dev = packed_info.shape[0], packed_info.device
-    lib, st = L.lib(), L.stream()
     cnt, start = (torch.empty(n_rays, dtype=torch.int32, device=dev) for _ in range(2))
     total = torch.empty(1, dtype=torch.int32, device=dev)          # written by the scan
     tmp = _resample_tmp(n_rays, vals.shape[0], n_samples, dev)
-    L.check(lib.ia_ray_resampling_merge_count(L.i64(n_rays), L.i64(vals.shape[0]), L.i32(n_samples), L.ptr(packed_info), L.ptr(vals),
-                                              L.ptr(il), L.ptr(ir), L.ptr(w), L.ptr(cnt), L.ptr(start), L.ptr(total), L.ptr(tmp),
-                                              L.ptr(L.scan_tmp(n_rays, dev)), st), "ia_ray_resampling_merge_count")
+    L.lib().ia_ray_resampling_merge_count(n_rays, vals.shape[0], n_samples, packed_info, vals, il, ir, w, cnt, start, total, tmp,
+                                          L.scan_tmp(n_rays, dev))
     T = int(total.item())
     ov = torch.empty(T, dtype=torch.float32, device=dev)
     ol, orr = torch.empty(T, dtype=torch.bool, device=dev), torch.empty(T, dtype=torch.bool, device=dev)
     ray = torch.empty(T, dtype=torch.int64, device=dev)
     pinfo = torch.empty((n_rays, 2), dtype=torch.int32, device=dev)
-    L.check(lib.ia_ray_resampling_merge_fill(L.i64(n_rays), L.i64(vals.shape[0]), L.i32(n_samples), L.ptr(packed_info), L.ptr(vals),
-                                             L.ptr(il), L.ptr(ir), L.ptr(cnt), L.ptr(start), L.ptr(ov), L.ptr(ol), L.ptr(orr), L.ptr(ray),
-                                             L.ptr(pinfo), L.ptr(tmp), st), "ia_ray_resampling_merge_fill")
+    L.lib().ia_ray_resampling_merge_fill(n_rays, vals.shape[0], n_samples, packed_info, vals, il, ir, cnt, start, ov, ol, orr, ray, pinfo, tmp)
     return ov, ol, orr, ray, pinfo
 
 
@@ -180,13 +168,9 @@ def _fine(packed_info, t_starts, t_ends, wa, sdfs, n_samples, sdf_mode, exact_si
     tmp = _resample_tmp(n_rays, wa.shape[0], n_samples, dev) if n_samples > 8 else None      # few points per ray stay in registers
     if sdf_mode:
         sd = _f32v(sdfs)
-        L.check(L.lib().ia_ray_resampling_sdf_fine(L.i64(n_rays), L.i64(wa.shape[0]), L.i32(n_samples), L.ptr(packed_info), L.ptr(st),
-                                                   L.ptr(en), L.ptr(wa), L.ptr(sd), L.ptr(rpi), L.i64(T), L.ptr(rs), L.ptr(re), L.ptr(fg),
-                                                   L.ptr(tmp), L.stream()), "ia_ray_resampling_sdf_fine")
+        L.lib().ia_ray_resampling_sdf_fine(n_rays, wa.shape[0], n_samples, packed_info, st, en, wa, sd, rpi, T, rs, re, fg, tmp)
     else:
-        L.check(L.lib().ia_ray_resampling_fine(L.i64(n_rays), L.i64(wa.shape[0]), L.i32(n_samples), L.ptr(packed_info), L.ptr(st),
-                                               L.ptr(en), L.ptr(wa), L.ptr(rpi), L.i64(T), L.ptr(rs), L.ptr(re), L.ptr(fg), L.ptr(tmp),
-                                               L.stream()), "ia_ray_resampling_fine")
+        L.lib().ia_ray_resampling_fine(n_rays, wa.shape[0], n_samples, packed_info, st, en, wa, rpi, T, rs, re, fg, tmp)
     return rpi, rs, re, fg
 
 
@@ -213,17 +197,14 @@ def compact_foreground(resampled_packed_info: Tensor, starts: Tensor, ends: Tens
     rpi = resampled_packed_info.to(torch.int32).contiguous()
     fg = is_fg.contiguous()
     st_, en_ = starts.reshape(-1).contiguous().float(), ends.reshape(-1).contiguous().float()
-    lib, st = L.lib(), L.stream()
     cnt, start = (torch.empty(n_rays, dtype=torch.int32, device=dev) for _ in range(2))
     total = torch.empty(1, dtype=torch.int32, device=dev)          # written by the scan
-    L.check(lib.ia_fg_count(L.i64(n_rays), L.ptr(rpi), L.ptr(fg), L.ptr(cnt), L.ptr(start), L.ptr(total), L.ptr(L.scan_tmp(n_rays, dev)), st),
-            "ia_fg_count")
+    L.lib().ia_fg_count(n_rays, rpi, fg, cnt, start, total, L.scan_tmp(n_rays, dev))
     F_ = int(total.item())
     ray_indices = torch.empty(F_, dtype=torch.int64, device=dev)
     ts, te = torch.empty(F_, device=dev), torch.empty(F_, device=dev)
     pinfo = torch.empty((n_rays, 2), dtype=torch.int32, device=dev)
-    L.check(lib.ia_fg_compact(L.i64(n_rays), L.ptr(rpi), L.ptr(fg), L.ptr(st_), L.ptr(en_), L.ptr(cnt), L.ptr(start), L.ptr(ray_indices),
-                              L.ptr(ts), L.ptr(te), L.ptr(pinfo), st), "ia_fg_compact")
+    L.lib().ia_fg_compact(n_rays, rpi, fg, st_, en_, cnt, start, ray_indices, ts, te, pinfo)
     return ray_indices, ts, te, pinfo
 
 
@@ -241,8 +222,7 @@ class IntervalSamples:
         if sv.shape[0] != self.t_starts.shape[0]:
             raise RuntimeError("to_edges: one value per sample expected")
         out = torch.empty(self.pos.shape[0], dtype=torch.float32, device=sv.device)
-        L.check(L.lib().ia_samples_to_edges(L.i64(out.shape[0]), L.ptr(self.is_left), L.ptr(self.pos), L.ptr(sv), L.f32(fill), L.ptr(out),
-                                            L.stream()), "ia_samples_to_edges")
+        L.lib().ia_samples_to_edges(out.shape[0], self.is_left, self.pos, sv, fill, out)
         return out
 
 
@@ -263,18 +243,14 @@ def interval_samples(packed_info: Tensor, vals: Tensor, is_left: Tensor, ray_ind
     n_rays, n_edges, dev = packed_info.shape[0], vals.shape[0], vals.device
     if il.shape[0] != n_edges or ray_indices.shape[0] != n_edges:
         raise RuntimeError("vals, is_left and ray_indices must have one entry per edge")
-    lib, st = L.lib(), L.stream()
     pos = torch.empty(n_edges, dtype=torch.int32, device=dev)
     total = torch.empty(1, dtype=torch.int32, device=dev)          # written by the scan
-    L.check(lib.ia_interval_samples_count(L.i64(n_edges), L.ptr(il), L.ptr(pos), L.ptr(total), L.ptr(L.scan_tmp(n_edges, dev)), st),
-            "ia_interval_samples_count")
+    L.lib().ia_interval_samples_count(n_edges, il, pos, total, L.scan_tmp(n_edges, dev))
     S = int(total.item())
     ts, te = torch.empty(S, dtype=torch.float32, device=dev), torch.empty(S, dtype=torch.float32, device=dev)
     ray = torch.empty(S, dtype=torch.int64, device=dev)
     pinfo = torch.empty((n_rays, 2), dtype=torch.int32, device=dev)
-    L.check(lib.ia_interval_samples_fill(L.i64(n_rays), L.i64(n_edges), L.ptr(packed_info), L.ptr(vals), L.ptr(ray_indices), L.ptr(il),
-                                         L.ptr(pos), L.ptr(total), L.ptr(None), L.ptr(ts), L.ptr(te), L.ptr(ray), L.ptr(pinfo), st),
-            "ia_interval_samples_fill")
+    L.lib().ia_interval_samples_fill(n_rays, n_edges, packed_info, vals, ray_indices, il, pos, total, None, ts, te, ray, pinfo)
     return IntervalSamples(il, pos, ts, te, ray, pinfo)
 
 
@@ -296,30 +272,24 @@ def ray_resampling_merge_compact_samples(packed_info: Tensor, vals: Tensor, is_l
     if cap == 0 or cap >= (1 << 31):
         ov, ol, orr, ray, pinfo = ray_resampling_merge_compact(packed_info, vals, il, ir, w, n_samples)
         return ov, ol, orr, ray, pinfo, interval_samples(pinfo, ov, ol, ray)
-    lib, st = L.lib(), L.stream()
     cnt, start = (torch.empty(n_rays, dtype=torch.int32, device=dev) for _ in range(2))
     totals = torch.empty(2, dtype=torch.int32, device=dev)          # [T, S], both written by scans
     tmp = _resample_tmp(n_rays, n_in, n_samples, dev)
-    L.check(lib.ia_ray_resampling_merge_count(L.i64(n_rays), L.i64(n_in), L.i32(n_samples), L.ptr(packed_info), L.ptr(vals),
-                                              L.ptr(il), L.ptr(ir), L.ptr(w), L.ptr(cnt), L.ptr(start), L.ptr(totals[0:1]), L.ptr(tmp),
-                                              L.ptr(L.scan_tmp(n_rays, dev)), st), "ia_ray_resampling_merge_count")
+    L.lib().ia_ray_resampling_merge_count(n_rays, n_in, n_samples, packed_info, vals, il, ir, w, cnt, start, totals[0:1], tmp,
+                                          L.scan_tmp(n_rays, dev))
     ov = torch.empty(cap, dtype=torch.float32, device=dev)
     ol, orr = torch.empty(cap, dtype=torch.bool, device=dev), torch.empty(cap, dtype=torch.bool, device=dev)
     ray = torch.empty(cap, dtype=torch.int64, device=dev)
     pinfo = torch.empty((n_rays, 2), dtype=torch.int32, device=dev)
-    L.check(lib.ia_ray_resampling_merge_fill(L.i64(n_rays), L.i64(n_in), L.i32(n_samples), L.ptr(packed_info), L.ptr(vals),
-                                             L.ptr(il), L.ptr(ir), L.ptr(cnt), L.ptr(start), L.ptr(ov), L.ptr(ol), L.ptr(orr), L.ptr(ray),
-                                             L.ptr(pinfo), L.ptr(tmp), st), "ia_ray_resampling_merge_fill")
+    L.lib().ia_ray_resampling_merge_fill(n_rays, n_in, n_samples, packed_info, vals, il, ir, cnt, start, ov, ol, orr, ray, pinfo, tmp)
     pos = torch.empty(cap, dtype=torch.int32, device=dev)
-    L.check(lib.ia_interval_samples_count_upto(L.i64(cap), L.ptr(ol), L.ptr(totals[0:1]), L.ptr(pos), L.ptr(totals[1:2]),
-                                               L.ptr(L.scan_tmp(cap, dev)), st), "ia_interval_samples_count_upto")
+    L.lib().ia_interval_samples_count_upto(cap, ol, totals[0:1], pos, totals[1:2], L.scan_tmp(cap, dev))
     T, S = totals.tolist()                                          # the one read-back of K2 + the samples of its result
     ov, ol, orr, ray, pos = ov[:T], ol[:T], orr[:T], ray[:T], pos[:T]
     ts, te = torch.empty(S, dtype=torch.float32, device=dev), torch.empty(S, dtype=torch.float32, device=dev)
     sray = torch.empty(S, dtype=torch.int64, device=dev)
     spinfo = torch.empty((n_rays, 2), dtype=torch.int32, device=dev)
-    L.check(lib.ia_interval_samples_fill(L.i64(n_rays), L.i64(T), L.ptr(pinfo), L.ptr(ov), L.ptr(ray), L.ptr(ol), L.ptr(pos), L.ptr(totals[1:2]),
-                                         L.ptr(None), L.ptr(ts), L.ptr(te), L.ptr(sray), L.ptr(spinfo), st), "ia_interval_samples_fill")
+    L.lib().ia_interval_samples_fill(n_rays, T, pinfo, ov, ray, ol, pos, totals[1:2], None, ts, te, sray, spinfo)
     return ov, ol, orr, ray, pinfo, IntervalSamples(ol, pos, ts, te, sray, spinfo)
 
 
@@ -347,9 +317,8 @@ def pack_info(ray_indices: Tensor, n_rays: int = None) -> Tensor:
     ray_indices = ray_indices.contiguous().to(torch.int64)
     dev = ray_indices.device
     out = torch.empty((n_rays, 2), dtype=torch.int32, device=dev)
-    tmp = L.work_area(L.lib().ia_pack_info_tmp_bytes(L.i64(n_rays)), dev)
-    L.check(L.lib().ia_pack_info(L.i64(ray_indices.shape[0]), L.ptr(ray_indices), L.i64(n_rays), L.ptr(out),
-                                 L.ptr(tmp), L.stream()), "ia_pack_info")
+    tmp = L.work_area(L.lib().ia_pack_info_tmp_bytes(n_rays), dev)
+    L.lib().ia_pack_info(ray_indices.shape[0], ray_indices, n_rays, out, tmp)
     return out
 
 
@@ -362,15 +331,13 @@ def unpack_info(packed_info: Tensor, n_samples: int) -> Tensor:
         raise NotImplementedError("Only support cuda inputs.")
     packed_info = _i32c(packed_info)
     out = torch.empty((n_samples,), dtype=torch.int64, device=packed_info.device)
-    L.check(L.lib().ia_unpack_info(L.i64(packed_info.shape[0]), L.ptr(packed_info), L.ptr(out), L.stream()),
-            "ia_unpack_info")
+    L.lib().ia_unpack_info(packed_info.shape[0], packed_info, out)
     return out
 
 
 def _unpack_info_to_mask(packed_info: Tensor, n_samples: int) -> Tensor:
     masks = torch.zeros((packed_info.shape[0], n_samples), dtype=torch.bool, device=packed_info.device)
-    L.check(L.lib().ia_unpack_info_to_mask(L.i64(packed_info.shape[0]), L.ptr(packed_info), L.i32(n_samples),
-                                           L.ptr(masks), L.stream()), "ia_unpack_info_to_mask")
+    L.lib().ia_unpack_info_to_mask(packed_info.shape[0], packed_info, n_samples, masks)
     return masks
 
 
@@ -394,8 +361,7 @@ class _UnpackData(torch.autograd.Function):
         else:
             raise NotImplementedError(f"unpack_data: dtype {data.dtype}")
         out = torch.zeros((packed_info.shape[0], n_samples, dim), dtype=torch.float32, device=data.device)
-        L.check(L.lib().ia_unpack_data(L.i64(packed_info.shape[0]), L.ptr(packed_info), L.i32(dim), L.ptr(words),
-                                       L.i32(n_samples), L.ptr(out), L.stream()), "ia_unpack_data")
+        L.lib().ia_unpack_data(packed_info.shape[0], packed_info, dim, words, n_samples, out)
         return out.view(orig_dtype)
 
     @staticmethod

@@ -51,11 +51,11 @@ def marching_cubes(level: torch.Tensor, threshold: float = 0.0, vmin: Optional[S
         raise TypeError("marching_cubes needs a float32 level grid")
     level = level.contiguous()
     nx, ny, nz = (int(s) for s in level.shape)
-    lib, st, dev = L.lib(), L.stream(), level.device
-    scratch = L.work_area(lib.ia_mc_scratch_bytes(L.i32(nx), L.i32(ny), L.i32(nz)), dev)
+    dev = level.device
+    scratch = L.work_area(L.lib().ia_mc_scratch_bytes(nx, ny, nz), dev)
     totals = torch.empty(2, dtype=torch.int64, device=dev)
-    thr = L.f32(float(threshold))
-    L.check(lib.ia_mc_count(L.i32(nx), L.i32(ny), L.i32(nz), L.ptr(level), thr, L.ptr(scratch), L.ptr(totals), st), "ia_mc_count")
+    thr = float(threshold)
+    L.lib().ia_mc_count(nx, ny, nz, level, thr, scratch, totals)
     n_v, n_t = (int(v) for v in totals.tolist())             # the one read-back: sizes of the outputs
     if n_v >= 2 ** 31:
         raise ValueError(f"marching_cubes: {n_v} vertices do not fit the int32 vertex-id table")
@@ -63,8 +63,7 @@ def marching_cubes(level: torch.Tensor, threshold: float = 0.0, vmin: Optional[S
     t_pos_idx = torch.empty((n_t, 3), dtype=torch.int64, device=dev)
     if n_v > 0:
         first_vid = torch.empty(nx * ny * nz, dtype=torch.int32, device=dev)
-        L.check(lib.ia_mc_emit(L.i32(nx), L.i32(ny), L.i32(nz), L.ptr(level), thr, _box(vmin, vmax), L.ptr(scratch), L.ptr(first_vid),
-                               L.ptr(v_pos), L.ptr(t_pos_idx), st), "ia_mc_emit")
+        L.lib().ia_mc_emit(nx, ny, nz, level, thr, _box(vmin, vmax), scratch, first_vid, v_pos, t_pos_idx)
     return {"v_pos": v_pos, "t_pos_idx": t_pos_idx}
 
 
@@ -93,12 +92,10 @@ def level_grid(geometry, resolution: int, vmin: torch.Tensor, vmax: torch.Tensor
     level = torch.empty(n, dtype=torch.float32, device=dev)
     chunk = max(1, min(int(chunk), n))
     xp = torch.empty((chunk, 3), dtype=torch.float32, device=dev)
-    lib = L.lib()
     center, scale = geometry.center.contiguous().float(), geometry.scale.contiguous().float()
     for start in range(0, n, chunk):
         m = min(chunk, n - start)
-        L.check(lib.ia_mc_grid_points(L.i64(m), L.i64(start), L.i32(R), L.i32(R), L.i32(R), L.ptr(axes), L.ptr(center), L.ptr(scale),
-                                      L.ptr(xp), L.stream()), "ia_mc_grid_points")
+        L.lib().ia_mc_grid_points(m, start, R, R, R, axes, center, scale, xp)
         level[start:start + m] = geometry.sdf_only(xp[:m], normalized=True)
     return level.view(R, R, R)
 
@@ -142,15 +139,13 @@ def vertex_faces(n_vertices: int, t_pos_idx: torch.Tensor):
         raise L.IaError("mesh.vertex_faces needs GPU tensors (no CPU fallback)")
     faces = t_pos_idx.reshape(-1, 3).contiguous().to(torch.int64)
     V, T = int(n_vertices), int(faces.shape[0])
-    lib, st, dev = L.lib(), L.stream(), faces.device
+    dev = faces.device
     offsets = torch.empty(V + 1, dtype=torch.int32, device=dev)
-    L.check(lib.ia_mesh_vertex_faces_count(L.i64(T), L.i64(V), L.ptr(faces), L.ptr(offsets), st), "ia_mesh_vertex_faces_count")
-    L.check(lib.ia_exclusive_scan_i32(L.ptr(offsets), L.ptr(offsets), L.ptr(None), L.i64(V + 1), L.ptr(L.scan_tmp(V + 1, dev)), st),
-            "ia_exclusive_scan_i32")
+    L.lib().ia_mesh_vertex_faces_count(T, V, faces, offsets)
+    L.lib().ia_exclusive_scan_i32(offsets, offsets, None, V + 1, L.scan_tmp(V + 1, dev))
     cursor = torch.empty(max(V, 1), dtype=torch.int32, device=dev)
     lists = torch.empty(max(3 * T, 1), dtype=torch.int32, device=dev)
-    L.check(lib.ia_mesh_vertex_faces_fill(L.i64(T), L.i64(V), L.ptr(faces), L.ptr(offsets), L.ptr(cursor), L.ptr(lists), st),
-            "ia_mesh_vertex_faces_fill")
+    L.lib().ia_mesh_vertex_faces_fill(T, V, faces, offsets, cursor, lists)
     return offsets, lists[:3 * T]
 
 
@@ -169,8 +164,7 @@ def vertex_normals(v_pos: torch.Tensor, t_pos_idx: torch.Tensor, return_lists: b
     V, T = int(v.shape[0]), int(faces.shape[0])
     offsets, lists = vertex_faces(V, faces)
     v_nrm = torch.empty((V, 3), dtype=torch.float32, device=v.device)
-    L.check(L.lib().ia_mesh_vertex_normals(L.i64(V), L.i64(T), L.ptr(v), L.ptr(faces), L.ptr(offsets), L.ptr(lists), L.ptr(v_nrm),
-                                           L.stream()), "ia_mesh_vertex_normals")
+    L.lib().ia_mesh_vertex_normals(V, T, v, faces, offsets, lists, v_nrm)
     return (v_nrm, offsets, lists) if return_lists else v_nrm
 
 

@@ -15,7 +15,6 @@ caller converts one.  A value that cannot be formed -- an empty mask, a rectangl
 NaN on the device and carries a status word next to it: `.item()`, `float()`, `.tolist()` and `.cpu()` of the returned MetricValue
 read value and status in ONE copy and raise ValueError then; to_host() does so for a whole dict of metrics with one copy in all.
 Every reduction is deterministic (DESIGN.md "Frame evaluation").  LPIPS is not provided."""
-import ctypes as C
 from typing import Dict, Optional
 
 import torch
@@ -116,8 +115,7 @@ def squared_error(inputs: Tensor, targets: Tensor, valid_mask: Optional[Tensor] 
     dev = a.device
     sums = torch.empty(2, dtype=torch.float64, device=dev)
     buf = torch.empty(2, dtype=torch.float32, device=dev)
-    L.check(L.lib().ia_metric_sq_err(L.i64(n), L.i32(c), L.ptr(a), L.ptr(b), L.ptr(_mask(valid_mask, n, "PSNR")), L.ptr(_tmp(dev)),
-                                     L.ptr(sums), L.ptr(buf), L.stream()), "ia_metric_sq_err")
+    L.lib().ia_metric_sq_err(n, c, a, b, _mask(valid_mask, n, "PSNR"), _tmp(dev), sums, buf)
     return sums, MetricValue.make(buf, 1, "PSNR")
 
 
@@ -143,9 +141,7 @@ def normal_error(inputs: Tensor, targets: Tensor, valid_mask: Optional[Tensor], 
     buf = torch.empty(2, dtype=torch.float32, device=dev)
     err = torch.empty(a.shape[:-1], dtype=torch.float32, device=dev) if want_map else None
     cam = torch.empty_like(a) if (want_camera and transform) else None
-    L.check(L.lib().ia_metric_normal_error(L.i64(n), L.ptr(a), L.ptr(b), L.ptr(_mask(valid_mask, n, "NormalError")), L.ptr(rot),
-                                           L.i32(int(transform)), L.i32(int(normalize)), L.ptr(cam), L.ptr(err), L.ptr(_tmp(dev)),
-                                           L.ptr(sums), L.ptr(buf), L.stream()), "ia_metric_normal_error")
+    L.lib().ia_metric_normal_error(n, a, b, _mask(valid_mask, n, "NormalError"), rot, int(transform), int(normalize), cam, err, _tmp(dev), sums, buf)
     return dict(mean=MetricValue.make(buf, 1, "NormalError"), sums=sums, map=err, camera=cam)
 
 
@@ -174,8 +170,7 @@ def transform_normals(normals: Tensor, w2c: Optional[Tensor] = None) -> Tensor:
     if a.shape[-1] != 3:
         raise ValueError(f"transform_normals: needs a [..., 3] map, got {tuple(a.shape)}")
     out = torch.empty_like(a)
-    L.check(L.lib().ia_metric_transform_normals(L.i64(a.numel() // 3), L.ptr(a), L.ptr(_rotation(w2c)), L.ptr(out), L.stream()),
-            "ia_metric_transform_normals")
+    L.lib().ia_metric_transform_normals(a.numel() // 3, a, _rotation(w2c), out)
     return out
 
 
@@ -187,8 +182,7 @@ def albedo_sums(gt_albedo: Tensor, pred_albedo: Tensor, gt_mask: Optional[Tensor
     n, dev = x.numel() // 3, x.device
     sums = torch.empty((3, 2), dtype=torch.float64, device=dev)
     buf = torch.empty(4, dtype=torch.float32, device=dev)
-    L.check(L.lib().ia_metric_albedo_sums(L.i64(n), L.ptr(x), L.ptr(xh), L.ptr(_mask(gt_mask, n, "compute_albedo_rescale_factor")),
-                                          L.ptr(_tmp(dev)), L.ptr(sums), L.ptr(buf), L.stream()), "ia_metric_albedo_sums")
+    L.lib().ia_metric_albedo_sums(n, x, xh, _mask(gt_mask, n, "compute_albedo_rescale_factor"), _tmp(dev), sums, buf)
     return sums, MetricValue.make(buf, 3, "compute_albedo_rescale_factor")
 
 
@@ -204,8 +198,7 @@ def align_albedo(gt_albedo: Tensor, pred_albedo: Tensor, gt_mask: Tensor, ratio:
     xh = _f32(pred_albedo, "align_albedo")
     n = xh.numel() // 3
     out = torch.empty_like(xh)
-    L.check(L.lib().ia_metric_albedo_apply(L.i64(n), L.ptr(xh), L.ptr(_mask(gt_mask, n, "align_albedo")), L.ptr(_f32(ratio, "align_albedo")),
-                                           L.ptr(out), L.stream()), "ia_metric_albedo_apply")
+    L.lib().ia_metric_albedo_apply(n, xh, _mask(gt_mask, n, "align_albedo"), _f32(ratio, "align_albedo"), out)
     return out, ratio
 
 
@@ -216,7 +209,7 @@ def mask_rect(mask: Tensor) -> Tensor:
     H, W = (int(s) for s in mask.shape)
     m = _mask(mask, H * W, "mask_rect")
     rect = torch.empty(4, dtype=torch.int32, device=mask.device)
-    L.check(L.lib().ia_metric_mask_rect(L.i32(H), L.i32(W), L.ptr(m), L.ptr(_tmp(mask.device)), L.ptr(rect), L.stream()), "ia_metric_mask_rect")
+    L.lib().ia_metric_mask_rect(H, W, m, _tmp(mask.device), rect)
     return rect
 
 
@@ -230,10 +223,10 @@ def ssim(inputs: Tensor, targets: Tensor, rect: Optional[Tensor] = None) -> Metr
         if not rect.is_cuda or rect.dtype != torch.int32 or rect.numel() != 4:
             raise ValueError("SSIM: rect must be 4 int32 values on the device (mask_rect's output)")
         rect = rect.contiguous()
-    lib, dev = L.lib(), a.device
-    tmp = L.work_area(lib.ia_metric_ssim_tmp_bytes(L.i32(H), L.i32(W), L.i32(Cn)), dev)
+    dev = a.device
+    tmp = L.work_area(L.lib().ia_metric_ssim_tmp_bytes(H, W, Cn), dev)
     buf = torch.empty(2, dtype=torch.float64, device=dev)
-    L.check(lib.ia_metric_ssim(L.i32(H), L.i32(W), L.i32(Cn), L.ptr(a), L.ptr(b), L.ptr(rect), L.ptr(tmp), L.ptr(buf), L.stream()), "ia_metric_ssim")
+    L.lib().ia_metric_ssim(H, W, Cn, a, b, rect, tmp, buf)
     return MetricValue.make(buf, 1, "SSIM")
 
 

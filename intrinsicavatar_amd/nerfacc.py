@@ -75,7 +75,7 @@ def pack_occupancy_bits(binaries: Tensor) -> Tensor:
         raise ValueError("binaries must be a bool tensor")
     n_cells = b.numel()
     bits = torch.empty((n_cells + 31) // 32, dtype=torch.int32, device=b.device)
-    L.check(L.lib().ia_occgrid_pack_bits(L.ptr(b), L.i64(n_cells), L.ptr(bits), L.stream()), "ia_occgrid_pack_bits")
+    L.lib().ia_occgrid_pack_bits(b, n_cells, bits)
     return bits
 
 
@@ -119,9 +119,7 @@ def traverse_grids(
     _, rx, ry, rz = binaries.shape
     if grid_bits is None:
         grid_bits = pack_occupancy_bits(binaries[0])
-    lib, st = L.lib(), L.stream()
-    args = (L.i64(n_rays), L.ptr(rays_o), L.ptr(rays_d), L.ptr(grid_bits), L.i32(rx), L.i32(ry), L.i32(rz), L.ptr(aabb),
-            L.ptr(near_planes), L.ptr(far_planes), L.f32(step_size), L.f32(cone_angle))
+    args = (n_rays, rays_o, rays_d, grid_bits, rx, ry, rz, aabb, near_planes, far_planes, step_size, cone_angle)
     # measured on MI355X (tools/microbench.py): the single launch wins for large batches (2M secondary rays: 0.74 vs
     # 1.20 ms), the two-phase protocol for one 540x540 frame of primary rays (0.14 vs 0.16 ms)
     method = method or os.environ.get("IA_TRAVERSE") or ("fused" if n_rays >= FUSED_MIN_RAYS else "two_pass")
@@ -130,13 +128,13 @@ def traverse_grids(
         if out is not None:
             return out
 
-    scratch = L.work_area(lib.ia_traverse_scratch_bytes(L.i64(n_rays)), dev)
+    scratch = L.work_area(L.lib().ia_traverse_scratch_bytes(n_rays), dev)
     pcnt = torch.empty(n_rays, dtype=torch.int64, device=dev)          # n_edges | n_samples << 32
     pstart = torch.empty(n_rays, dtype=torch.int64, device=dev)
     total = torch.empty(1, dtype=torch.int64, device=dev)               # written by the scan
-    L.check(lib.ia_traverse_grids_count(*args, L.ptr(scratch), L.ptr(pcnt), st), "ia_traverse_grids_count")
+    L.lib().ia_traverse_grids_count(*args, scratch, pcnt)
     tmp = L.scan_tmp(n_rays, dev)
-    L.check(lib.ia_exclusive_scan_i64(L.ptr(pcnt), L.ptr(pstart), L.ptr(total), L.i64(n_rays), L.ptr(tmp), st), "scan")
+    L.lib().ia_exclusive_scan_i64(pcnt, pstart, total, n_rays, tmp)
     tot = int(total.item())                      # the one host sync of the two-phase protocol
     E, S = tot & 0xFFFFFFFF, tot >> 32
 
@@ -147,9 +145,7 @@ def traverse_grids(
     sm_ray = torch.empty(S, dtype=torch.int64, device=dev)
     term = torch.empty(n_rays, dtype=torch.float32, device=dev)
     pinfo = torch.empty((2, n_rays, 2), dtype=torch.int64, device=dev)
-    L.check(lib.ia_traverse_grids_fill(*args, L.ptr(scratch), L.ptr(pcnt), L.ptr(pstart), L.ptr(pinfo[0]), L.ptr(pinfo[1]),
-                                       L.ptr(iv_vals), L.ptr(iv_flags[0]), L.ptr(iv_flags[1]), L.ptr(iv_ray),
-                                       L.ptr(sm_vals), L.ptr(sm_ray), L.ptr(term), st), "ia_traverse_grids_fill")
+    L.lib().ia_traverse_grids_fill(*args, scratch, pcnt, pstart, pinfo[0], pinfo[1], iv_vals, iv_flags[0], iv_flags[1], iv_ray, sm_vals, sm_ray, term)
     intervals = RayIntervals(vals=iv_vals, packed_info=pinfo[0], ray_indices=iv_ray,
                              is_left=iv_flags[0], is_right=iv_flags[1])
     samples = RaySamples(vals=sm_vals, packed_info=pinfo[1], ray_indices=sm_ray, all_valid=True)
@@ -180,8 +176,7 @@ def _traverse_fused(args, n_rays, aabb, step_size, max_extent, dev, incoherent=F
     cap_e = cap_s + 8 * n_rays
     if cap_e >= (1 << 31):
         return None
-    lib, st = L.lib(), L.stream()
-    scratch = L.work_area(lib.ia_traverse_fused_scratch_bytes(L.i64(n_rays)), dev)
+    scratch = L.work_area(L.lib().ia_traverse_fused_scratch_bytes(n_rays), dev)
     totals = torch.empty(3, dtype=torch.int64, device=dev)
     iv_vals = torch.empty(cap_e, dtype=torch.float32, device=dev)
     iv_flags = torch.empty((2, cap_e), dtype=torch.bool, device=dev)
@@ -191,11 +186,8 @@ def _traverse_fused(args, n_rays, aabb, step_size, max_extent, dev, incoherent=F
     sm_ends = torch.empty((2, cap_s), dtype=torch.float32, device=dev)
     term = torch.empty(n_rays, dtype=torch.float32, device=dev) if termination_planes else None
     pinfo = torch.empty((2, n_rays, 2), dtype=torch.int64, device=dev)
-    L.check(lib.ia_traverse_grids_fused(*args, L.ptr(scratch), L.i64(cap_e), L.i64(cap_s), L.ptr(totals), L.ptr(pinfo[0]),
-                                        L.ptr(pinfo[1]), L.ptr(iv_vals), L.ptr(iv_flags[0]), L.ptr(iv_flags[1]), L.ptr(iv_ray),
-                                        L.ptr(sm_vals), L.ptr(sm_ray), L.ptr(term), L.ptr(sm_ends[0]), L.ptr(sm_ends[1]),
-                                        L.i32(max(smax, 2) if incoherent else 0), st),
-            "ia_traverse_grids_fused")
+    L.lib().ia_traverse_grids_fused(*args, scratch, cap_e, cap_s, totals, pinfo[0], pinfo[1], iv_vals, iv_flags[0], iv_flags[1], iv_ray, sm_vals,
+                                    sm_ray, term, sm_ends[0], sm_ends[1], max(smax, 2) if incoherent else 0)
     E, S, ovf = (int(v) for v in totals.tolist())          # the one host sync (output sizes are data dependent)
     if ovf:
         return None
@@ -221,8 +213,7 @@ class _WeightFromAlpha(torch.autograd.Function):
         alphas = alphas.contiguous().float()
         w = torch.empty_like(alphas)
         t = torch.empty_like(alphas)
-        L.check(L.lib().ia_render_weight_from_alpha(L.i64(packed_info.shape[0]), L.ptr(packed_info), L.ptr(alphas),
-                                                    L.ptr(w), L.ptr(t), L.stream()), "ia_render_weight_from_alpha")
+        L.lib().ia_render_weight_from_alpha(packed_info.shape[0], packed_info, alphas, w, t)
         ctx.save_for_backward(alphas, packed_info, w, t)
         ctx.set_materialize_grads(False)          # an unused output's gradient arrives as None (NULL in the kernel), not as a zero fill
         return w, t
@@ -233,9 +224,7 @@ class _WeightFromAlpha(torch.autograd.Function):
         gw = gw.contiguous().float() if gw is not None else None
         gt = gt.contiguous().float() if gt is not None else None
         ga = torch.empty_like(alphas)
-        L.check(L.lib().ia_render_weight_from_alpha_bwd(
-            L.i64(packed_info.shape[0]), L.ptr(packed_info), L.ptr(alphas), L.ptr(w), L.ptr(t), L.ptr(gw), L.ptr(gt),
-            L.ptr(ga), L.stream()), "ia_render_weight_from_alpha_bwd")
+        L.lib().ia_render_weight_from_alpha_bwd(packed_info.shape[0], packed_info, alphas, w, t, gw, gt, ga)
         return ga, None
 
 
@@ -297,8 +286,7 @@ class _Accumulate(torch.autograd.Function):
             out = torch.zeros((n_rays, dim), dtype=torch.float32, device=weights.device)      # as "values omitted")
         else:
             out = torch.empty((n_rays, dim), dtype=torch.float32, device=weights.device)
-            L.check(L.lib().ia_accumulate_along_rays(L.i64(n_rays), L.ptr(packed_info), L.i32(dim), L.ptr(weights),
-                                                     L.ptr(values), L.ptr(out), L.stream()), "ia_accumulate_along_rays")
+            L.lib().ia_accumulate_along_rays(n_rays, packed_info, dim, weights, values, out)
         ctx.save_for_backward(weights, values, ray_indices)
         ctx.dim = dim
         return out
@@ -312,9 +300,7 @@ class _Accumulate(torch.autograd.Function):
         gv = torch.empty_like(values) if need_v else None
         if weights.shape[0] == 0:
             return gw, gv, None, None
-        L.check(L.lib().ia_accumulate_along_rays_bwd(
-            L.i64(weights.shape[0]), L.i32(ctx.dim), L.ptr(ray_indices), L.ptr(weights), L.ptr(values), L.ptr(g),
-            L.ptr(gw), L.ptr(gv), L.stream()), "ia_accumulate_along_rays_bwd")
+        L.lib().ia_accumulate_along_rays_bwd(weights.shape[0], ctx.dim, ray_indices, weights, values, g, gw, gv)
         return gw, gv, None, None
 
 

@@ -21,10 +21,8 @@ def binarize(occs: Tensor, resolution, thre_max: float, keep_largest_component: 
     dev = occs.device
     binaries = torch.empty((rx, ry, rz), dtype=torch.bool, device=dev)
     thre = torch.empty(1, device=dev)
-    tmp = L.work_area(L.lib().ia_occgrid_tmp_bytes(L.i32(rx), L.i32(ry), L.i32(rz)), dev)
-    L.check(L.lib().ia_occgrid_binarize(L.i32(rx), L.i32(ry), L.i32(rz), L.ptr(occs), L.f32(thre_max),
-                                        L.i32(int(keep_largest_component)), L.ptr(binaries), L.ptr(thre), L.ptr(tmp), L.stream()),
-            "ia_occgrid_binarize")
+    tmp = L.work_area(L.lib().ia_occgrid_tmp_bytes(rx, ry, rz), dev)
+    L.lib().ia_occgrid_binarize(rx, ry, rz, occs, thre_max, int(keep_largest_component), binaries, thre, tmp)
     return binaries, thre
 
 
@@ -118,8 +116,7 @@ class TemporalOccGridEstimator(torch.nn.Module):
         occ = occ_eval_fn(x).reshape(-1).contiguous().float()
         sl = slice(lvl * self.cells_per_lvl, (lvl + 1) * self.cells_per_lvl)
         occs_lvl = self.occs[sl]
-        L.check(L.lib().ia_occgrid_ema(L.i64(self.cells_per_lvl), L.ptr(occs_lvl), L.ptr(occ), L.f32(ema_decay), L.stream()),
-                "ia_occgrid_ema")
+        L.lib().ia_occgrid_ema(self.cells_per_lvl, occs_lvl, occ, ema_decay)
         self.binaries[lvl], _ = binarize(occs_lvl, self.resolution.tolist(), occ_thre, keep_largest_component=True)
         self._bits.pop(lvl, None)
 

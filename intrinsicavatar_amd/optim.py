@@ -91,8 +91,7 @@ class Adam(torch.optim.Optimizer):
                 P[i], G[i] = L.ptr(p).value, L.ptr(g).value
                 M[i], V[i] = L.ptr(st["exp_avg"]).value, L.ptr(st["exp_avg_sq"]).value
                 N[i], S[i], W[i] = p.numel(), step_size, wd
-            L.check(L.lib().ia_adam_step(L.i32(n), P, G, M, V, N, S, W, L.f32(b1), L.f32(b2), L.f32(eps), L.f32(bc2_sqrt),
-                                         L.f32(self.grad_scale), L.stream()), "ia_adam_step")
+            L.lib().ia_adam_step(n, P, G, M, V, N, S, W, b1, b2, eps, bc2_sqrt, self.grad_scale)
         if batches:
             from . import fields
             fields.params_changed()          # the kernel wrote the parameters through raw pointers: Tensor._version did not move

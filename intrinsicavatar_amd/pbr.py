@@ -12,7 +12,6 @@ import math
 import os
 from typing import Dict, Optional
 
-import ctypes as C
 
 import torch
 from torch import Tensor
@@ -105,9 +104,8 @@ class EnvironmentLightTensor(torch.nn.Module):
         if H * W <= self.PDF_KERNEL_MAX_PIXELS:
             self.pmf = torch.empty((H, W), device=base.device)
             self._cdf = torch.empty(H * W, dtype=torch.float64, device=base.device)
-            tmp = L.work_area(L.lib().ia_envlight_pdf_tables_tmp_bytes(L.i32(H), L.i32(W)), base.device)
-            L.check(L.lib().ia_envlight_pdf_tables(L.i32(H), L.i32(W), L.ptr(base), L.ptr(self.pmf), L.ptr(self._cdf), L.ptr(tmp), L.stream()),
-                    "ia_envlight_pdf_tables")
+            tmp = L.work_area(L.lib().ia_envlight_pdf_tables_tmp_bytes(H, W), base.device)
+            L.lib().ia_envlight_pdf_tables(H, W, base, self.pmf, self._cdf, tmp)
         else:        # larger than the kernel's tile table: the torch expression
             sin_t = torch.sin((torch.arange(H, device=base.device) + 0.5) * math.pi / H)[:, None]
             lum = (0.2126 * base[..., 0] + 0.7152 * base[..., 1] + 0.0722 * base[..., 2]).clamp_min(0).double()
@@ -129,8 +127,7 @@ class EnvironmentLightTensor(torch.nn.Module):
         out = torch.empty((k, 3), device=dev)
         rot = None if w2s_rot is None else w2s_rot.detach().float().contiguous()
         _, cdf = self._pdf_tables()
-        L.check(L.lib().ia_envlight_sample(L.i64(k), L.ptr(u), L.ptr(cdf), L.i32(H), L.i32(W), L.ptr(rot), L.ptr(out),
-                                           L.stream()), "ia_envlight_sample")
+        L.lib().ia_envlight_sample(k, u, cdf, H, W, rot, out)
         return out
 
     def _eval(self, d: Tensor, want_rgb: bool, want_pdf: bool):
@@ -140,8 +137,7 @@ class EnvironmentLightTensor(torch.nn.Module):
         pdf = torch.empty((n,), device=d.device) if want_pdf else None
         H, W, _ = self.base.shape
         pmf = self._pdf_tables()[0] if want_pdf else None
-        L.check(L.lib().ia_envlight_eval(L.i64(n), L.ptr(d), L.ptr(self.base.detach()), L.ptr(pmf), L.i32(H), L.i32(W), L.ptr(rgb),
-                                         L.ptr(pdf), L.stream()), "ia_envlight_eval")
+        L.lib().ia_envlight_eval(n, d, self.base.detach(), pmf, H, W, rgb, pdf)
         return rgb, pdf
 
     def eval(self, d_world: Tensor) -> Tensor:
@@ -163,7 +159,7 @@ class _SGImage(torch.autograd.Function):
         axis, log_lambda, mu = axis.contiguous().float(), log_lambda.contiguous().float(), mu.contiguous().float()
         K = axis.shape[0]
         out = torch.empty((H, W, 3), device=axis.device)
-        L.check(L.lib().ia_sg_image(L.i32(K), L.i32(H), L.i32(W), L.ptr(axis), L.ptr(log_lambda), L.ptr(mu), L.ptr(out), L.stream()), "ia_sg_image")
+        L.lib().ia_sg_image(K, H, W, axis, log_lambda, mu, out)
         ctx.save_for_backward(axis, log_lambda, mu)
         ctx.hw = (H, W)
         return out
@@ -173,10 +169,9 @@ class _SGImage(torch.autograd.Function):
         axis, log_lambda, mu = ctx.saved_tensors
         K = axis.shape[0]
         H, W = ctx.hw
-        tmp = L.work_area(L.lib().ia_sg_image_bwd_tmp_bytes(L.i32(K)), axis.device)
+        tmp = L.work_area(L.lib().ia_sg_image_bwd_tmp_bytes(K), axis.device)
         g_axis, g_ll, g_mu = torch.empty_like(axis), torch.empty_like(log_lambda), torch.empty_like(mu)
-        L.check(L.lib().ia_sg_image_bwd(L.i32(K), L.i32(H), L.i32(W), L.ptr(axis), L.ptr(log_lambda), L.ptr(mu), L.ptr(g_img.contiguous().float()),
-                                        L.ptr(tmp), L.ptr(g_axis), L.ptr(g_ll), L.ptr(g_mu), L.stream()), "ia_sg_image_bwd")
+        L.lib().ia_sg_image_bwd(K, H, W, axis, log_lambda, mu, g_img.contiguous().float(), tmp, g_axis, g_ll, g_mu)
         return g_axis, g_ll, g_mu, None, None
 
 
@@ -275,8 +270,7 @@ def transform_dirs_s2w(dirs_smpl: Tensor, w2s_rot: Tensor) -> Tensor:
     """snarf_deformer.py:154-158: normalize(d @ w2s[:3,:3]) -- the world directions ia_envlight_background looks up (same device function)."""
     d = dirs_smpl.detach().reshape(-1, 3).float().contiguous()
     out = torch.empty_like(d)
-    L.check(L.lib().ia_transform_dirs_s2w(L.i64(d.shape[0]), L.ptr(d), L.ptr(w2s_rot.detach().float().contiguous()), L.ptr(out), L.stream()),
-            "ia_transform_dirs_s2w")
+    L.lib().ia_transform_dirs_s2w(d.shape[0], d, w2s_rot.detach().float().contiguous(), out)
     return out
 
 
@@ -290,8 +284,7 @@ class _EmitterBackground(torch.autograd.Function):
             raise L.IaError(f"w2s_rot must be [3,3], got {tuple(rot.shape)}")
         H, W, _ = base.shape
         out = torch.empty((d.shape[0], 3), device=base.device)
-        L.check(L.lib().ia_envlight_background(L.i64(d.shape[0]), L.ptr(d), L.ptr(rot), L.ptr(base), L.i32(H), L.i32(W), L.ptr(out), L.stream()),
-                "ia_envlight_background")
+        L.lib().ia_envlight_background(d.shape[0], d, rot, base, H, W, out)
         ctx.save_for_backward(d, rot)
         ctx.hw = (H, W)
         return out
@@ -307,8 +300,7 @@ class _EmitterBackground(torch.autograd.Function):
         if n:
             acc = torch.empty((H, W, 3), dtype=torch.int64, device=d.device)          # the fixed-point image and the bits of max |g|
             gmax = torch.empty(1, dtype=torch.int32, device=d.device)
-            L.check(L.lib().ia_envlight_background_bwd(L.i64(n), L.ptr(d), L.ptr(rot), L.ptr(g_out.float().contiguous()), L.i32(H), L.i32(W),
-                                                       L.ptr(g_base), L.ptr(acc), L.ptr(gmax), L.stream()), "ia_envlight_background_bwd")
+            L.lib().ia_envlight_background_bwd(n, d, rot, g_out.float().contiguous(), H, W, g_base, acc, gmax)
         return g_base, None, None
 
 
@@ -358,12 +350,9 @@ def pbr_shade(mode: str, normal, albedo, roughness, metallic, view_dirs, out_dir
     vis = torch.empty((F_, 3), device=dev) if mode == "uniform_light" else None
     H, W, _ = emitter.base.shape
     c = lambda t: None if t is None else t.contiguous().float()     # noqa: E731
-    L.check(L.lib().ia_pbr_shade(
-        L.i32(MODES[mode]), L.i64(F_), L.ptr(c(normal)), L.ptr(c(albedo)), L.ptr(c(roughness.reshape(-1))),
-        L.ptr(c(metallic.reshape(-1))), L.ptr(c(view_dirs)), L.ptr(c(out_dirs)), L.ptr(c(transmittance.reshape(-1))),
-        L.ptr(c(indirect_rgb)), L.ptr(c(inv_pdf.reshape(-1)) if inv_pdf is not None else None), L.ptr(emitter.base),
-        L.ptr(_pmf_of(emitter)), L.i32(H), L.i32(W), L.ptr(c(w2s_rot)), L.ptr(Lo), L.ptr(Ld), L.ptr(Ls), L.ptr(vis), L.stream()),
-        "ia_pbr_shade")
+    L.lib().ia_pbr_shade(MODES[mode], F_, c(normal), c(albedo), c(roughness.reshape(-1)), c(metallic.reshape(-1)), c(view_dirs), c(out_dirs),
+                         c(transmittance.reshape(-1)), c(indirect_rgb), c(inv_pdf.reshape(-1)) if inv_pdf is not None else None, emitter.base,
+                         _pmf_of(emitter), H, W, c(w2s_rot), Lo, Ld, Ls, vis)
     return (Lo, Ld, Ls, vis) if mode == "uniform_light" else (Lo, Ld, Ls)
 
 
@@ -381,10 +370,8 @@ class _PbrShade(torch.autograd.Function):
         F_ = normal.shape[0]
         Lo, Ld, Ls = (torch.empty((F_, 3), device=normal.device) for _ in range(3))
         H, W, _ = env_base.shape
-        L.check(L.lib().ia_pbr_shade(L.i32(mode), L.i64(F_), L.ptr(normal), L.ptr(albedo), L.ptr(roughness), L.ptr(metallic),
-                                     L.ptr(view_dirs), L.ptr(out_dirs), L.ptr(tr), L.ptr(ind), L.ptr(inv_pdf), L.ptr(env_base),
-                                     L.ptr(env_pmf), L.i32(H), L.i32(W), L.ptr(w2s_rot), L.ptr(Lo), L.ptr(Ld), L.ptr(Ls),
-                                     L.ptr(None), L.stream()), "ia_pbr_shade")
+        L.lib().ia_pbr_shade(mode, F_, normal, albedo, roughness, metallic, view_dirs, out_dirs, tr, ind, inv_pdf, env_base, env_pmf, H, W, w2s_rot,
+                             Lo, Ld, Ls, None)
         ctx.mode = mode
         ctx.save_for_backward(normal, albedo, roughness, metallic, env_base, view_dirs, out_dirs, tr, ind, inv_pdf, env_pmf, w2s_rot)
         ctx.set_materialize_grads(False)
@@ -400,13 +387,10 @@ class _PbrShade(torch.autograd.Function):
         g_r, g_m = torch.empty(F_, device=dev), torch.empty(F_, device=dev)
         g_base = L.zeros_like(env_base) if ctx.needs_input_grad[5] else None
         H, W, _ = env_base.shape
-        nb = int(L.lib().ia_pbr_shade_bwd_scratch_bytes(L.i64(F_))) if g_base is not None else 0
+        nb = int(L.lib().ia_pbr_shade_bwd_scratch_bytes(F_)) if g_base is not None else 0
         scratch = L.work_area(nb, dev) if nb else None
-        L.check(L.lib().ia_pbr_shade_bwd(
-            L.i32(ctx.mode), L.i64(F_), L.ptr(normal), L.ptr(albedo), L.ptr(roughness), L.ptr(metallic), L.ptr(view_dirs),
-            L.ptr(out_dirs), L.ptr(tr), L.ptr(ind), L.ptr(inv_pdf), L.ptr(env_base), L.ptr(env_pmf), L.i32(H), L.i32(W),
-            L.ptr(w2s_rot), L.ptr(c(g_Lo)), L.ptr(c(g_Ld)), L.ptr(c(g_Ls)), L.ptr(g_n), L.ptr(g_a), L.ptr(g_r), L.ptr(g_m),
-            L.ptr(g_base), L.ptr(scratch), C.c_size_t(nb), L.stream()), "ia_pbr_shade_bwd")
+        L.lib().ia_pbr_shade_bwd(ctx.mode, F_, normal, albedo, roughness, metallic, view_dirs, out_dirs, tr, ind, inv_pdf, env_base, env_pmf, H, W,
+                                 w2s_rot, c(g_Lo), c(g_Ld), c(g_Ls), g_n, g_a, g_r, g_m, g_base, scratch, nb)
         return (None, g_n, g_a, g_r[:, None], g_m[:, None], g_base, None, None, None, None, None, None, None)
 
 
@@ -424,18 +408,16 @@ def brdf_sample(normal, view_dirs, roughness, u):
     """scatterer.sample: out directions from the multi-lobe BRDF (u [F,3] uniforms)."""
     F_ = normal.shape[0]
     out = torch.empty((F_, 3), device=normal.device)
-    L.check(L.lib().ia_brdf_sample(L.i64(F_), L.ptr(normal.contiguous().float()), L.ptr(view_dirs.contiguous().float()),
-                                   L.ptr(roughness.reshape(-1).contiguous().float()), L.ptr(u.contiguous().float()), L.ptr(out),
-                                   L.stream()), "ia_brdf_sample")
+    L.lib().ia_brdf_sample(F_, normal.contiguous().float(), view_dirs.contiguous().float(), roughness.reshape(-1).contiguous().float(),
+                           u.contiguous().float(), out)
     return out
 
 
 def brdf_pdf(normal, view_dirs, out_dirs, roughness):
     F_ = normal.shape[0]
     out = torch.empty((F_,), device=normal.device)
-    L.check(L.lib().ia_brdf_pdf(L.i64(F_), L.ptr(normal.contiguous().float()), L.ptr(view_dirs.contiguous().float()),
-                                L.ptr(out_dirs.contiguous().float()), L.ptr(roughness.reshape(-1).contiguous().float()),
-                                L.ptr(out), L.stream()), "ia_brdf_pdf")
+    L.lib().ia_brdf_pdf(F_, normal.contiguous().float(), view_dirs.contiguous().float(), out_dirs.contiguous().float(),
+                        roughness.reshape(-1).contiguous().float(), out)
     return out[:, None]
 
 
@@ -449,8 +431,7 @@ def uniform_sphere_stratified(n_theta: int, n_phi: int, u: Tensor):
         raise RuntimeError("uniform_sphere_stratified: u must be [n_theta * n_phi, 2]")
     u2 = u[:K, :2].contiguous().float()
     dirs, inv_pdf = torch.empty((K, 3), device=dev), torch.empty((K, 1), device=dev)
-    L.check(L.lib().ia_uniform_sphere_stratified(L.i32(n_theta), L.i32(n_phi), L.ptr(u2), L.ptr(dirs), L.ptr(inv_pdf), L.stream()),
-            "ia_uniform_sphere_stratified")
+    L.lib().ia_uniform_sphere_stratified(n_theta, n_phi, u2, dirs, inv_pdf)
     return dirs, inv_pdf
 
 
@@ -462,11 +443,8 @@ def pbr_light_shade(normal, albedo, roughness, metallic, view_dirs, light_dirs, 
     Lo, Ld, Ls = (torch.empty((F_, 3), device=dev) for _ in range(3))
     H, W, _ = emitter.base.shape
     c = lambda t: None if t is None else t.contiguous().float()     # noqa: E731
-    L.check(L.lib().ia_pbr_light_shade(
-        L.i64(F_), L.ptr(c(normal)), L.ptr(c(albedo)), L.ptr(c(roughness.reshape(-1))), L.ptr(c(metallic.reshape(-1))),
-        L.ptr(c(view_dirs)), L.ptr(c(light_dirs)), L.ptr(c(transmittance.reshape(-1))), L.ptr(c(indirect_rgb)),
-        L.ptr(emitter.base), L.ptr(_pmf_of(emitter)), L.i32(H), L.i32(W), L.ptr(c(w2s_rot)), L.ptr(Lo), L.ptr(Ld), L.ptr(Ls),
-        L.stream()), "ia_pbr_light_shade")
+    L.lib().ia_pbr_light_shade(F_, c(normal), c(albedo), c(roughness.reshape(-1)), c(metallic.reshape(-1)), c(view_dirs), c(light_dirs),
+                               c(transmittance.reshape(-1)), c(indirect_rgb), emitter.base, _pmf_of(emitter), H, W, c(w2s_rot), Lo, Ld, Ls)
     return Lo, Ld, Ls
 
 
@@ -498,17 +476,14 @@ class VolumeInteraction:
              self.surface_idx) = lib_nerfacc.ray_resampling(self.packed_info, t_starts[:, None], t_ends[:, None], weights.detach(),
                                                             sdfs.detach(), spp)
         self.S = int(weights.shape[0])
-        lib, st = L.lib(), L.stream()
         self.fg_ray_cnt = torch.empty(n_rays, dtype=torch.int32, device=dev)
-        L.check(lib.ia_vi_layout(L.i64(n_rays), L.i32(spp), L.ptr(self.resampled_packed_info), L.ptr(self.bg_counts),
-                                 L.ptr(self.fg_ray_cnt), st), "ia_vi_layout")
+        L.lib().ia_vi_layout(n_rays, spp, self.resampled_packed_info, self.bg_counts, self.fg_ray_cnt)
         self.fg_start = torch.empty(n_rays, dtype=torch.int32, device=dev)
         tmp = L.scan_tmp(max(n_rays, self.S), dev)
-        L.check(lib.ia_exclusive_scan_i32(L.ptr(self.fg_ray_cnt), L.ptr(self.fg_start), L.ptr(totals[1:2]), L.i64(n_rays), L.ptr(tmp), st),
-                "scan")
+        L.lib().ia_exclusive_scan_i32(self.fg_ray_cnt, self.fg_start, totals[1:2], n_rays, tmp)
         self.fg_off = torch.empty(self.S, dtype=torch.int32, device=dev)          # per source interval (gather backward)
         tot2 = torch.empty(1, dtype=torch.int32, device=dev)
-        L.check(lib.ia_exclusive_scan_i32(L.ptr(self.fg_counts), L.ptr(self.fg_off), L.ptr(tot2), L.i64(self.S), L.ptr(tmp), st), "scan")
+        L.lib().ia_exclusive_scan_i32(self.fg_counts, self.fg_off, tot2, self.S, tmp)
         if capacity:
             self.R, self.F = totals.tolist()                            # one read-back for both sizes
             self.ts, self.offsets, self.sampled_idx = self.ts[:self.R], self.offsets[:self.R], self.sampled_idx[:self.R]
@@ -535,11 +510,9 @@ class VolumeInteraction:
         bg = torch.empty(self.R - self.F, dtype=torch.int64, device=dev)
         rri = torch.empty(self.R, dtype=torch.int64, device=dev)
         rw = torch.zeros(self.R, device=dev) if want_weights else None
-        L.check(L.lib().ia_vi_indices(L.i64(self.n_rays), L.i32(self.spp), L.ptr(self.resampled_packed_info), L.ptr(self.fg_ray_cnt),
-                                      L.ptr(self.fg_start), L.ptr(self.bg_counts), L.ptr(self.sampled_idx), L.ptr(self.fg_counts),
-                                      L.ptr(weights.detach().float().contiguous()),
-                                      L.ptr(transmittance.detach().reshape(-1).float().contiguous()), L.ptr(fg), L.ptr(bg), L.ptr(rri),
-                                      L.ptr(rw), L.stream()), "ia_vi_indices")
+        L.lib().ia_vi_indices(self.n_rays, self.spp, self.resampled_packed_info, self.fg_ray_cnt, self.fg_start, self.bg_counts, self.sampled_idx,
+                              self.fg_counts, weights.detach().float().contiguous(), transmittance.detach().reshape(-1).float().contiguous(), fg, bg,
+                              rri, rw)
         return fg, bg, rri, rw
 
     @torch.no_grad()
@@ -549,8 +522,7 @@ class VolumeInteraction:
         out = torch.empty(self.F, dtype=torch.int32, device=self.ts.device)
         u = shuffle_u.float().contiguous()
         assert u.shape == (self.n_rays, self.spp)
-        L.check(L.lib().ia_light_shuffle(L.i64(self.n_rays), L.i32(self.spp), L.ptr(self.fg_ray_cnt), L.ptr(self.fg_start), L.ptr(u),
-                                         L.ptr(out), L.stream()), "ia_light_shuffle")
+        L.lib().ia_light_shuffle(self.n_rays, self.spp, self.fg_ray_cnt, self.fg_start, u, out)
         return out
 
 
@@ -565,12 +537,9 @@ class _VIGather(torch.autograd.Function):
         vi.positions, vi.view_dirs = torch.empty((F_, 3), device=dev), torch.empty((F_, 3), device=dev)
         o_n, o_a = torch.empty((F_, 3), device=dev), torch.empty((F_, 3), device=dev)
         o_r, o_m, o_w = torch.empty((F_, 1), device=dev), torch.empty((F_, 1), device=dev), torch.empty(F_, device=dev)
-        L.check(L.lib().ia_vi_gather(
-            L.i64(vi.n_rays), L.ptr(vi.resampled_packed_info), L.ptr(vi.fg_ray_cnt), L.ptr(vi.fg_start), L.ptr(vi.ts),
-            L.ptr(vi.sampled_idx), L.ptr(vi.fg_counts), L.ptr(c(weights)), L.ptr(c(rays_o)), L.ptr(c(rays_d)), L.ptr(c(normals)),
-            L.ptr(c(albedo)), L.ptr(c(roughness.reshape(-1))), L.ptr(c(metallic.reshape(-1))), L.ptr(vi.fg_src), L.ptr(vi.fg_ray),
-            L.ptr(vi.positions), L.ptr(vi.view_dirs), L.ptr(o_n), L.ptr(o_a), L.ptr(o_r), L.ptr(o_m), L.ptr(o_w), L.stream()),
-            "ia_vi_gather")
+        L.lib().ia_vi_gather(vi.n_rays, vi.resampled_packed_info, vi.fg_ray_cnt, vi.fg_start, vi.ts, vi.sampled_idx, vi.fg_counts, c(weights),
+                             c(rays_o), c(rays_d), c(normals), c(albedo), c(roughness.reshape(-1)), c(metallic.reshape(-1)), vi.fg_src, vi.fg_ray,
+                             vi.positions, vi.view_dirs, o_n, o_a, o_r, o_m, o_w)
         ctx.vi = vi
         ctx.shapes = (roughness.shape, metallic.shape)
         return o_w, o_n, o_a, o_r, o_m
@@ -582,10 +551,8 @@ class _VIGather(torch.autograd.Function):
         c = lambda t: None if t is None else t.float().contiguous()      # noqa: E731
         G_n, G_a = torch.empty((S, 3), device=dev), torch.empty((S, 3), device=dev)
         G_r, G_m, G_w = torch.empty(S, device=dev), torch.empty(S, device=dev), torch.empty(S, device=dev)
-        L.check(L.lib().ia_vi_gather_bwd(L.i64(S), L.ptr(vi.fg_counts), L.ptr(vi.fg_off), L.ptr(c(g_n)), L.ptr(c(g_a)),
-                                         L.ptr(c(g_r.reshape(-1)) if g_r is not None else None),
-                                         L.ptr(c(g_m.reshape(-1)) if g_m is not None else None), L.ptr(c(g_w)), L.ptr(G_n), L.ptr(G_a),
-                                         L.ptr(G_r), L.ptr(G_m), L.ptr(G_w), L.stream()), "ia_vi_gather_bwd")
+        L.lib().ia_vi_gather_bwd(S, vi.fg_counts, vi.fg_off, c(g_n), c(g_a), c(g_r.reshape(-1)) if g_r is not None else None,
+                                 c(g_m.reshape(-1)) if g_m is not None else None, c(g_w), G_n, G_a, G_r, G_m, G_w)
         return None, None, None, G_w, G_n, G_a, G_r.reshape(ctx.shapes[0]), G_m.reshape(ctx.shapes[1])
 
 
@@ -602,9 +569,7 @@ class _VIComposite(torch.autograd.Function):
             if tuple(bgr.shape) != (vi.n_rays, 3):
                 raise L.IaError(f"background_rays must be [{vi.n_rays}, 3], got {tuple(bgr.shape)}")
         rgb = torch.empty((vi.n_rays, 3), device=dev)
-        L.check(L.lib().ia_vi_composite(L.i64(vi.n_rays), L.ptr(vi.resampled_packed_info), L.ptr(vi.fg_ray_cnt), L.ptr(vi.fg_start),
-                                        L.ptr(vi.bg_counts), L.ptr(w_fg), L.ptr(Lo), L.ptr(T), L.ptr(bg), L.ptr(bgr), L.ptr(rgb),
-                                        L.stream()), "ia_vi_composite")
+        L.lib().ia_vi_composite(vi.n_rays, vi.resampled_packed_info, vi.fg_ray_cnt, vi.fg_start, vi.bg_counts, w_fg, Lo, T, bg, bgr, rgb)
         ctx.vi = vi
         ctx.t_shape = transmittance.shape
         ctx.save_for_backward(w_fg, Lo, bg, bgr, T if bgr is not None else None)
@@ -619,14 +584,11 @@ class _VIComposite(torch.autograd.Function):
         g_w = torch.empty(vi.F, device=dev) if ctx.needs_input_grad[1] else None
         g_Lo = torch.empty((vi.F, 3), device=dev) if ctx.needs_input_grad[2] else None
         g_T = torch.empty(vi.n_rays, device=dev) if ctx.needs_input_grad[3] else None
-        L.check(L.lib().ia_vi_composite_bwd(L.i64(vi.n_rays), L.i64(vi.F), L.ptr(vi.resampled_packed_info), L.ptr(vi.bg_counts),
-                                            L.ptr(vi.fg_ray), L.ptr(w_fg), L.ptr(Lo), L.ptr(bg), L.ptr(bgr), L.ptr(g_rgb), L.ptr(g_w), L.ptr(g_Lo),
-                                            L.ptr(g_T), L.stream()), "ia_vi_composite_bwd")
+        L.lib().ia_vi_composite_bwd(vi.n_rays, vi.F, vi.resampled_packed_info, vi.bg_counts, vi.fg_ray, w_fg, Lo, bg, bgr, g_rgb, g_w, g_Lo, g_T)
         g_bgr = None
         if bgr is not None and ctx.needs_input_grad[5]:
             g_bgr = torch.empty((vi.n_rays, 3), device=dev)
-            L.check(L.lib().ia_vi_composite_bwd_bg(L.i64(vi.n_rays), L.ptr(vi.resampled_packed_info), L.ptr(vi.bg_counts), L.ptr(T),
-                                                   L.ptr(g_rgb), L.ptr(g_bgr), L.stream()), "ia_vi_composite_bwd_bg")
+            L.lib().ia_vi_composite_bwd_bg(vi.n_rays, vi.resampled_packed_info, vi.bg_counts, T, g_rgb, g_bgr)
         return None, g_w, g_Lo, (g_T.reshape(ctx.t_shape) if g_T is not None else None), None, g_bgr
 
 
@@ -637,20 +599,18 @@ def secondary_rays(normals: Tensor, positions: Tensor, dirs: Tensor, dir_index: 
     returns (rays_o [M,3], rays_d [M,3], src int32 [M] -> index into the F points, out_dirs [F,3])."""
     F_ = normals.shape[0]
     dev = normals.device
-    lib, st = L.lib(), L.stream()
     normals, positions, dirs = normals.detach().float().contiguous(), positions.float().contiguous(), dirs.float().contiguous()
     flag = torch.empty(F_, dtype=torch.int32, device=dev)
-    L.check(lib.ia_secondary_mask(L.i64(F_), L.ptr(normals), L.ptr(dirs), L.ptr(dir_index), L.ptr(flag), st), "ia_secondary_mask")
+    L.lib().ia_secondary_mask(F_, normals, dirs, dir_index, flag)
     slot = torch.empty(F_, dtype=torch.int32, device=dev)
     total = torch.empty(1, dtype=torch.int32, device=dev)          # written by the scan
     tmp = L.scan_tmp(F_, dev)
-    L.check(lib.ia_exclusive_scan_i32(L.ptr(flag), L.ptr(slot), L.ptr(total), L.i64(F_), L.ptr(tmp), st), "scan")
+    L.lib().ia_exclusive_scan_i32(flag, slot, total, F_, tmp)
     M = int(total.item())
     ro, rd = torch.empty((M, 3), device=dev), torch.empty((M, 3), device=dev)
     src = torch.empty(M, dtype=torch.int32, device=dev)
     dense = torch.empty((F_, 3), device=dev) if dir_index is not None else None
-    L.check(lib.ia_secondary_compact(L.i64(F_), L.ptr(flag), L.ptr(slot), L.ptr(positions), L.ptr(dirs), L.ptr(dir_index), L.ptr(ro),
-                                     L.ptr(rd), L.ptr(src), L.ptr(dense), st), "ia_secondary_compact")
+    L.lib().ia_secondary_compact(F_, flag, slot, positions, dirs, dir_index, ro, rd, src, dense)
     _FLAG_SLOT[id(src)] = (src, flag, slot)          # for scatter_secondary: the dense result is written point by point from (flag, slot)
     while len(_FLAG_SLOT) > 2:                        # (an entry keeps [F] int32 x 2 alive: released on use, two unused ones at most)
         _FLAG_SLOT.pop(next(iter(_FLAG_SLOT)))
@@ -670,13 +630,11 @@ def scatter_secondary(F_: int, src: Tensor, tr: Tensor, rgb: Tensor):
     trc, rgbc = tr.reshape(-1).float().contiguous(), rgb.float().contiguous()
     if ent is not None and ent[0] is src and ent[1].shape[0] == F_:
         d_tr, d_rgb = torch.empty((F_, 1), device=dev), torch.empty((F_, 3), device=dev)
-        L.check(L.lib().ia_secondary_gather_dense(L.i64(F_), L.ptr(ent[1]), L.ptr(ent[2]), L.ptr(trc), L.ptr(rgbc), L.ptr(d_tr), L.ptr(d_rgb),
-                                                  L.stream()), "ia_secondary_gather_dense")
+        L.lib().ia_secondary_gather_dense(F_, ent[1], ent[2], trc, rgbc, d_tr, d_rgb)
         return d_tr, d_rgb
     buf = L.zeros(F_ * 4, dev)                     # one fill for both
     d_tr, d_rgb = buf[:F_].view(F_, 1), buf[F_:].view(F_, 3)
-    L.check(L.lib().ia_secondary_scatter(L.i64(src.shape[0]), L.ptr(src), L.ptr(trc), L.ptr(rgbc), L.ptr(d_tr), L.ptr(d_rgb), L.stream()),
-            "ia_secondary_scatter")
+    L.lib().ia_secondary_scatter(src.shape[0], src, trc, rgbc, d_tr, d_rgb)
     return d_tr, d_rgb
 
 
@@ -718,8 +676,7 @@ def light_shuffle(n_rays: int, spp: int, resampled_packed_info: Tensor, fg_indic
     cnt = torch.where(rpi[:, 1] > 0, torch.full_like(rpi[:, 1], spp), torch.zeros_like(rpi[:, 1])).contiguous()
     start = (torch.cumsum(cnt, 0) - cnt).to(torch.int32).contiguous()
     full = torch.empty(int(cnt.sum()), dtype=torch.int32, device=dev)
-    L.check(L.lib().ia_light_shuffle(L.i64(n_rays), L.i32(spp), L.ptr(cnt), L.ptr(start), L.ptr(shuffle_u.float().contiguous()),
-                                     L.ptr(full), L.stream()), "ia_light_shuffle")
+    L.lib().ia_light_shuffle(n_rays, spp, cnt, start, shuffle_u.float().contiguous(), full)
     return full[fg_indices].long()
 
 
@@ -735,8 +692,7 @@ class _ScattererEval(torch.autograd.Function):
         dev = n.device
         keep = [t.detach().float().contiguous() for t in (n, wi, wo, alpha.reshape(-1), albedo, metallic.reshape(-1))]
         diff, spec = torch.empty((P, 1), device=dev), torch.empty((P, 3), device=dev)
-        L.check(L.lib().ia_scatterer_eval(L.i64(P), L.i32(lobes), *[L.ptr(t) for t in keep], L.ptr(diff), L.ptr(spec), L.stream()),
-                "ia_scatterer_eval")
+        L.lib().ia_scatterer_eval(P, lobes, *keep, diff, spec)
         ctx.lobes = lobes
         ctx.shapes = (alpha.shape, metallic.shape)
         ctx.save_for_backward(*keep)
@@ -759,10 +715,8 @@ class _ScattererEval(torch.autograd.Function):
         g_env = torch.zeros((1, 1, 3), device=dev)
         view = (-wi).contiguous()
         # Li = 0 * em + ind_rgb = 1, weight = inv_pdf = 1  ->  Lo_diff = diff, Lo_spec = spec
-        L.check(L.lib().ia_pbr_shade_bwd(L.i32(1), L.i64(P), L.ptr(n), L.ptr(albedo), L.ptr(alpha), L.ptr(metallic), L.ptr(view),
-                                         L.ptr(wo), L.ptr(zeros), L.ptr(ones3), L.ptr(ones), L.ptr(env), L.ptr(pmf), L.i32(1), L.i32(1),
-                                         L.ptr(eye), L.ptr(None), L.ptr(g_Ld), L.ptr(g_Ls), L.ptr(g_n), L.ptr(g_a), L.ptr(g_r),
-                                         L.ptr(g_m), L.ptr(g_env), L.ptr(None), C.c_size_t(0), L.stream()), "ia_pbr_shade_bwd")
+        L.lib().ia_pbr_shade_bwd(1, P, n, albedo, alpha, metallic, view, wo, zeros, ones3, ones, env, pmf, 1, 1, eye, None, g_Ld, g_Ls, g_n, g_a, g_r,
+                                 g_m, g_env, None, 0)
         if ctx.lobes == 1:       # the cosine lobe does not depend on the material
             g_a, g_r, g_m = torch.zeros_like(g_a), torch.zeros_like(g_r), torch.zeros_like(g_m)
         return None, g_n, None, None, g_r.reshape(ctx.shapes[0]), g_a, g_m.reshape(ctx.shapes[1])
@@ -796,8 +750,7 @@ class _Scatterer(torch.nn.Module):
             u = torch.rand((P, 3), device=dev)
         keep = [t.detach().float().contiguous() for t in (n, wi, self._alpha(alpha_x, alpha_y), u)]
         out = torch.empty((P, 3), device=dev)
-        L.check(L.lib().ia_scatterer_sample(L.i64(P), L.i32(self.LOBES), *[L.ptr(t) for t in keep], L.ptr(out), L.stream()),
-                "ia_scatterer_sample")
+        L.lib().ia_scatterer_sample(P, self.LOBES, *keep, out)
         return out
 
     @torch.no_grad()
@@ -805,8 +758,7 @@ class _Scatterer(torch.nn.Module):
         P, dev = n.shape[0], n.device
         keep = [t.detach().float().contiguous() for t in (n, wi, wo, self._alpha(alpha_x, alpha_y))]
         out = torch.empty((P, 1), device=dev)
-        L.check(L.lib().ia_scatterer_pdf(L.i64(P), L.i32(self.LOBES), *[L.ptr(t) for t in keep], L.ptr(out), L.stream()),
-                "ia_scatterer_pdf")
+        L.lib().ia_scatterer_pdf(P, self.LOBES, *keep, out)
         return out
 
     def eval(self, wi, n, wo, alpha_x, alpha_y=None, albedo=None, metallic=None, attenuation=None):

@@ -23,7 +23,7 @@ def knn_points_flat(p1: Tensor, p2: Tensor, K: int):
     P, V = p1.shape[0], p2.shape[0]
     d2 = torch.empty((P, K), dtype=torch.float32, device=p1.device)
     idx = torch.empty((P, K), dtype=torch.int32, device=p1.device)
-    L.check(L.lib().ia_knn_points(L.i64(P), L.i32(V), L.i32(K), L.ptr(p1), L.ptr(p2), L.ptr(d2), L.ptr(idx), L.stream()), "ia_knn_points")
+    L.lib().ia_knn_points(P, V, K, p1, p2, d2, idx)
     return d2, idx
 
 

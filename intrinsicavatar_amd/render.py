@@ -28,8 +28,7 @@ from .nerfacc import RayIntervals
 def ray_points(rays_o: Tensor, rays_d: Tensor, ray_indices: Tensor, t0: Tensor, t1: Optional[Tensor] = None) -> Tensor:
     n = ray_indices.shape[0]
     pts = torch.empty((n, 3), device=rays_o.device)
-    L.check(L.lib().ia_ray_points(L.i64(n), L.ptr(rays_o), L.ptr(rays_d), L.ptr(ray_indices), L.ptr(t0), L.ptr(t1),
-                                  L.ptr(pts), L.stream()), "ia_ray_points")
+    L.lib().ia_ray_points(n, rays_o, rays_d, ray_indices, t0, t1, pts)
     return pts
 
 
@@ -38,16 +37,14 @@ def laplace_alpha(sdf: Tensor, dists, beta: Tensor) -> Tensor:
     n = sdf.shape[0]
     alpha = torch.empty_like(sdf)
     d_t, d_c = (dists, 0.0) if isinstance(dists, Tensor) else (None, float(dists))
-    L.check(L.lib().ia_laplace_alpha(L.i64(n), L.ptr(sdf), L.ptr(d_t), L.f32(d_c), L.ptr(beta), L.ptr(alpha), L.stream()),
-            "ia_laplace_alpha")
+    L.lib().ia_laplace_alpha(n, sdf, d_t, d_c, beta, alpha)
     return alpha
 
 
 def laplace_alpha_intervals(sdf: Tensor, t_starts: Tensor, t_ends: Tensor, beta: Tensor) -> Tensor:
     """laplace_alpha(sdf, t_ends - t_starts, beta) without materialising the difference (ia_laplace_alpha_intervals: bit-identical)."""
     alpha = torch.empty_like(sdf)
-    L.check(L.lib().ia_laplace_alpha_intervals(L.i64(sdf.shape[0]), L.ptr(sdf), L.ptr(t_starts.contiguous()), L.ptr(t_ends.contiguous()), L.ptr(beta),
-                                               L.ptr(alpha), L.stream()), "ia_laplace_alpha_intervals")
+    L.lib().ia_laplace_alpha_intervals(sdf.shape[0], sdf, t_starts.contiguous(), t_ends.contiguous(), beta, alpha)
     return alpha
 
 
@@ -55,8 +52,7 @@ def shade_prep(sdf_grad: Tensor, rays_d: Tensor, ray_indices: Tensor, w2s_rot: T
     n = sdf_grad.shape[0]
     dev = sdf_grad.device
     ns, nw, rf = (torch.empty((n, 3), device=dev) for _ in range(3))
-    L.check(L.lib().ia_shade_prep(L.i64(n), L.ptr(sdf_grad), L.ptr(rays_d), L.ptr(ray_indices), L.ptr(w2s_rot), L.ptr(ns),
-                                  L.ptr(nw), L.ptr(rf), L.stream()), "ia_shade_prep")
+    L.lib().ia_shade_prep(n, sdf_grad, rays_d, ray_indices, w2s_rot, ns, nw, rf)
     return ns, nw, rf
 
 
@@ -146,12 +142,10 @@ class RenderStep:
         import ctypes as C
         lo, inv_cell = self._sort_grid_params()
         origin = (C.c_float * 3)(*lo)
-        lib, st = L.lib(), L.stream()
         order = torch.empty(n, dtype=torch.int32, device=pts.device)
-        nb = int(lib.ia_morton_order_tmp_bytes(L.i64(n)))
+        nb = int(L.lib().ia_morton_order_tmp_bytes(n))
         tmp = L.work_area(nb, pts.device, "morton")                            # 256-byte aligned (a fresh allocation's base)
-        L.check(lib.ia_morton_order(L.i64(n), L.ptr(pts), origin, L.f32(inv_cell), L.i32(self.SORT_DROP_BITS), L.ptr(order), L.ptr(tmp),
-                                    C.c_size_t(nb), st), "ia_morton_order")
+        L.lib().ia_morton_order(n, pts, origin, inv_cell, self.SORT_DROP_BITS, order, tmp, nb)
         return order
 
     @torch.no_grad()
@@ -201,8 +195,7 @@ class RenderStep:
                     pts = ray_points(rays_o, rays_d, intervals.ray_indices, vals)
                     sdf = self._sdf_at(pts)
                     sdf_merge = torch.empty_like(sdf)          # is_left ? min(sdf, next sdf) : 1e10, one launch
-                    L.check(L.lib().ia_edge_min_sdf(L.i64(sdf.shape[0]), L.ptr(sdf), L.ptr(intervals.is_left), L.ptr(sdf_merge), L.stream()),
-                            "ia_edge_min_sdf")
+                    L.lib().ia_edge_min_sdf(sdf.shape[0], sdf, intervals.is_left, sdf_merge)
                     alphas = laplace_alpha(sdf_merge, self.render_step_size, beta)
                 else:              # alpha_fn: SDF at interval mid-points
                     smp = smp_next            # (came back with K2's result: one read-back for the edge count and the sample count)
@@ -490,7 +483,7 @@ class RenderStep:
                 # 1.5 ns -> 1.1 ns per point in the search): per-point work is order-free, only alpha and rgb go back to ray order
                 order = self._spatial_order(pts)
                 ps = torch.empty_like(pts)
-                L.check(L.lib().ia_gather_rows3_i32(L.i64(np_), L.ptr(pts), L.ptr(order), L.ptr(ps), L.stream()), "ia_gather_rows3_i32")
+                L.lib().ia_gather_rows3_i32(np_, pts, order, ps)
                 ol = order.long()
                 ri_s, dt_s = ray_indices[ol], (t_ends - t_starts)[ol]
                 d = self.deformer.deform(ps, self.geometry, with_grad=True, with_feature=True)
@@ -498,8 +491,8 @@ class RenderStep:
                 a_s = laplace_alpha(d["sdf"], dt_s, beta)
                 rgbs_s = self.radiance(d["pts_cano"], d["feature"], refl01, normal_world).contiguous()
                 a, rgbs = torch.empty_like(a_s), torch.empty_like(rgbs_s)
-                L.check(L.lib().ia_scatter_f32_i32(L.i64(np_), L.ptr(a_s), L.ptr(order), L.ptr(a), L.stream()), "ia_scatter_f32_i32")
-                L.check(L.lib().ia_scatter_rows3_i32(L.i64(np_), L.ptr(rgbs_s), L.ptr(order), L.ptr(rgbs), L.stream()), "ia_scatter_rows3_i32")
+                L.lib().ia_scatter_f32_i32(np_, a_s, order, a)
+                L.lib().ia_scatter_rows3_i32(np_, rgbs_s, order, rgbs)
             else:
                 d = self.deformer.deform(pts, self.geometry, with_grad=True, with_feature=True)
                 _, normal_world, refl01 = shade_prep(d["sdf_grad"], rd, ray_indices, w2s_rot)

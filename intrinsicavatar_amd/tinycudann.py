@@ -10,7 +10,6 @@ models/utils.py:12,130):
 tiny-cuda-nn is not vendored in the reference tree; semantics follow the published Instant-NGP definitions
 (oracle/ia_oracle_field.c).  All compute is libia_amd.so.  Third-order terms (d^2 enc / d x^2 is zero almost
 everywhere for linear interpolation) are not propagated, as in tiny-cuda-nn."""
-import ctypes as C
 
 import torch
 import torch.nn as nn
@@ -29,8 +28,7 @@ def _jac_contract(mode, jac, v, out_cols):
     n, K, _ = jac.shape
     v = v.contiguous().float()
     out = torch.empty((n, out_cols), device=jac.device)
-    L.check(L.lib().ia_hashgrid_jac_contract(L.i32(mode), L.i64(n), L.i32(K), L.ptr(jac), L.ptr(v), L.i32(v.stride(0)),
-                                             L.ptr(out), L.i32(out_cols), L.stream()), "ia_hashgrid_jac_contract")
+    L.lib().ia_hashgrid_jac_contract(mode, n, K, jac, v, v.stride(0), out, out_cols)
     return out
 
 
@@ -89,7 +87,7 @@ class _SH4(Function):
         if not (gy.dtype == torch.float32 and gy.dim() == 2 and gy.stride(1) == 1):      # a column block of a wider gradient row is read in place
             gy = gy.contiguous().float()
         gx = torch.empty_like(x)
-        L.check(L.lib().ia_sh4_bwd(L.i64(x.shape[0]), L.ptr(x), C.c_void_p(gy.data_ptr()), L.i32(gy.stride(0)), L.ptr(gx), L.stream()), "ia_sh4_bwd")
+        L.lib().ia_sh4_bwd(x.shape[0], x, L.base_ptr(gy), gy.stride(0), gx)
         return gx
 
 

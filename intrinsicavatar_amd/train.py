@@ -16,7 +16,6 @@ reference (resampling under no_grad; torch.gather passes gradients to the winnin
 weight-gradient reductions dW = G^T A ([64 x n] x [n x <=68]) use the split-K MFMA kernel ia_wgrad (rocBLAS maps this
 shape to a single output tile walking K = millions of points).
 """
-import ctypes as C
 import math
 import os
 from typing import Dict, Optional
@@ -38,31 +37,19 @@ def wgrad(G: Tensor, M: int, A: Tensor, N: int, want_bias: bool = True):
     dev = G.device
     dW = torch.zeros((M, N), device=dev)
     db = torch.zeros(M, device=dev) if want_bias else None
-    L.check(L.lib().ia_wgrad(L.i64(G.shape[0]), L.ptr(G), L.i32(G.stride(0)), L.i32(M), L.ptr(A), L.i32(A.stride(0)), L.i32(N),
-                             L.ptr(dW), L.i32(N), L.ptr(db), L.stream()), "ia_wgrad")
+    L.lib().ia_wgrad(G.shape[0], G, G.stride(0), M, A, A.stride(0), N, dW, N, db)
     return dW, db
+
+
+_segs = L.segments       # the segment table of the MLP entry points, under the name the backward Functions (and their tests) call it by
 
 
 def _jac_contract_T(jac: Tensor, v: Tensor) -> Tensor:
     """out[n,3] = sum_k v[n,k] * jac[n,k,:]   (d L / d x' from d L / d enc; ia_hashgrid_jac_contract mode 0)."""
     n, K = jac.shape[0], jac.shape[1]
     out = torch.empty((n, 3), device=jac.device)
-    L.check(L.lib().ia_hashgrid_jac_contract(L.i32(0), L.i64(n), L.i32(K), L.ptr(jac), C.c_void_p(v.data_ptr()),
-                                             L.i32(v.stride(0)), L.ptr(out), L.i32(3), L.stream()), "ia_hashgrid_jac_contract")
+    L.lib().ia_hashgrid_jac_contract(0, n, K, jac, L.base_ptr(v), v.stride(0), out, 3)
     return out
-
-
-def _segs(segs):
-    ns = len(segs)
-    ptrs = (C.c_void_p * ns)()
-    strides = (C.c_int * ns)()
-    widths = (C.c_int * ns)()
-    muls = (C.c_float * ns)()
-    adds = (C.c_float * ns)()
-    for i, (t, w, m, a) in enumerate(segs):
-        assert t.is_cuda and t.dtype == torch.float32 and t.stride(-1) == 1
-        ptrs[i], strides[i], widths[i], muls[i], adds[i] = t.data_ptr(), t.stride(0), w, m, a
-    return ns, ptrs, strides, widths, muls, adds
 
 
 class _SDFField(Function):
@@ -92,10 +79,7 @@ class _SDFField(Function):
             dW1k, db1, dW2, db2 = zeros_like_shapes([(64, 35), (64,), (13, 64), (13,)], dev)
             want_x = ctx.needs_input_grad[0]
             g_xyz = torch.empty((n, 3), device=dev) if want_x else None
-            L.check(L.lib().ia_sdf_mlp_bwd_fused(L.i64(n), L.i32(ns), ptrs, strides, widths, muls, adds, L.ptr(W1k), L.ptr(b1),
-                                                 L.ptr(W2), L.ptr(b2), L.ptr(jac), L.ptr(g_y), L.ptr(q), L.ptr(gE), L.ptr(gG),
-                                                 L.ptr(dW1k), L.ptr(db1), L.ptr(dW2), L.ptr(db2), L.ptr(g_xyz), L.stream()),
-                    "ia_sdf_mlp_bwd_fused")
+            L.lib().ia_sdf_mlp_bwd_fused(n, ns, ptrs, strides, widths, muls, adds, W1k, b1, W2, b2, jac, g_y, q, gE, gG, dW1k, db1, dW2, db2, g_xyz)
             fields.hashgrid_backward(xp, gE, g_table, g_jac=gG, q=q, level_mask=ctx.level_bits)
             g_x = None
             if want_x:
@@ -107,10 +91,7 @@ class _SDFField(Function):
             raise NotImplementedError("pose gradients (d L / d x_cano) are only produced by the fused backward (FUSED_WGRAD)")
         Hh, U = torch.empty((n, 36), device=dev), torch.empty((n, 36), device=dev)
         DZ, GZ, A, DGS = (torch.empty((n, 64), device=dev) for _ in range(4))
-        L.check(L.lib().ia_sdf_mlp_bwd(L.i64(n), L.i32(ns), ptrs, strides, widths, muls, adds, L.ptr(W1k), L.ptr(b1),
-                                       L.ptr(W2), L.ptr(b2), L.ptr(jac), L.ptr(g_y), L.ptr(q), L.ptr(gE), L.ptr(gG),
-                                       L.ptr(Hh), L.ptr(U), L.ptr(DZ), L.ptr(GZ), L.ptr(A), L.ptr(DGS), L.stream()),
-                "ia_sdf_mlp_bwd")
+        L.lib().ia_sdf_mlp_bwd(n, ns, ptrs, strides, widths, muls, adds, W1k, b1, W2, b2, jac, g_y, q, gE, gG, Hh, U, DZ, GZ, A, DGS)
         fields.hashgrid_backward(xp, gE, g_table, g_jac=gG, q=q, level_mask=ctx.level_bits)
         dW1k, db1 = wgrad(DZ, 64, Hh, 35)
         dW1k = dW1k + wgrad(GZ, 64, U, 35, want_bias=False)[0]
@@ -135,8 +116,7 @@ class _ShadePrep(Function):
         cg = lambda t: t.contiguous() if t is not None else None      # noqa: E731  (a missing gradient is NULL: zero inside the kernel)
         out = torch.empty_like(sdf_grad)
         # g_ns: normal_smpl = g / max(|g|, 1e-6), read by the BRDF of the PBR branch only
-        L.check(L.lib().ia_shade_prep_bwd(L.i64(n), L.ptr(sdf_grad), L.ptr(rays_d), L.ptr(ray_indices), L.ptr(w2s_rot),
-                                          L.ptr(cg(g_nw)), L.ptr(cg(g_rf)), L.ptr(cg(g_ns)), L.ptr(out), L.stream()), "ia_shade_prep_bwd")
+        L.lib().ia_shade_prep_bwd(n, sdf_grad, rays_d, ray_indices, w2s_rot, cg(g_nw), cg(g_rf), cg(g_ns), out)
         return out, None, None, None
 
 
@@ -150,9 +130,7 @@ class _SelectPush(Function):
         out, grad_c = out.contiguous(), grad_c.contiguous()
         feat, sdf = torch.empty((n, 13), device=dev), torch.empty(n, device=dev)
         sdf_grad, c2w = torch.empty((n, 3), device=dev), torch.empty((n, 3, 3), device=dev)
-        L.check(L.lib().ia_select_push(L.i64(n), L.ptr(out), L.ptr(grad_c), L.ptr(valid), L.ptr(fwd_J), L.ptr(cand_src),
-                                       L.ptr(sel), L.ptr(feat), L.ptr(sdf), L.ptr(sdf_grad), L.ptr(c2w), L.stream()),
-                "ia_select_push")
+        L.lib().ia_select_push(n, out, grad_c, valid, fwd_J, cand_src, sel, feat, sdf, sdf_grad, c2w)
         ctx.save_for_backward(valid, c2w)
         ctx.mark_non_differentiable(c2w)
         ctx.set_materialize_grads(False)
@@ -164,8 +142,7 @@ class _SelectPush(Function):
         n, dev = valid.shape[0], valid.device
         cg = lambda t: t.contiguous() if t is not None else None      # noqa: E731
         g_out, g_gc = torch.empty((n, 13), device=dev), torch.empty((n, 3), device=dev)
-        L.check(L.lib().ia_select_push_bwd(L.i64(n), L.ptr(valid), L.ptr(c2w), L.ptr(cg(g_feat)), L.ptr(cg(g_sdf)),
-                                           L.ptr(cg(g_sdf_grad)), L.ptr(g_out), L.ptr(g_gc), L.stream()), "ia_select_push_bwd")
+        L.lib().ia_select_push_bwd(n, valid, c2w, cg(g_feat), cg(g_sdf), cg(g_sdf_grad), g_out, g_gc)
         return g_out, g_gc, None, None, None, None
 
 
@@ -176,9 +153,9 @@ class _Eikonal(Function):
     def forward(ctx, sdf_grad, valid):
         n = sdf_grad.shape[0]
         sdf_grad = sdf_grad.contiguous()
-        k = int(L.lib().ia_eikonal_partials(L.i64(n)))
+        k = int(L.lib().ia_eikonal_partials(n))
         part = torch.zeros((max(k, 1), 2), device=sdf_grad.device)
-        L.check(L.lib().ia_eikonal(L.i64(n), L.ptr(sdf_grad), L.ptr(valid), L.ptr(part), L.stream()), "ia_eikonal")
+        L.lib().ia_eikonal(n, sdf_grad, valid, part)
         ctx.save_for_backward(sdf_grad, valid)
         tot = part.sum(0)
         ctx.mark_non_differentiable(tot[1])
@@ -189,8 +166,7 @@ class _Eikonal(Function):
         sdf_grad, valid = ctx.saved_tensors
         out = torch.empty_like(sdf_grad)
         w = g_sum.reshape(1).float().contiguous()
-        L.check(L.lib().ia_eikonal_bwd(L.i64(sdf_grad.shape[0]), L.ptr(sdf_grad), L.ptr(valid), L.ptr(w), L.ptr(out), L.stream()),
-                "ia_eikonal_bwd")
+        L.lib().ia_eikonal_bwd(sdf_grad.shape[0], sdf_grad, valid, w, out)
         return out, None
 
 
@@ -203,9 +179,9 @@ class _EikonalPartials(Function):
     def forward(ctx, sdf_grad, valid):
         n = sdf_grad.shape[0]
         sdf_grad = sdf_grad.contiguous()
-        k = int(L.lib().ia_eikonal_partials(L.i64(n)))
+        k = int(L.lib().ia_eikonal_partials(n))
         part = torch.empty((k, 2), device=sdf_grad.device) if k > 0 else torch.zeros((1, 2), device=sdf_grad.device)
-        L.check(L.lib().ia_eikonal(L.i64(n), L.ptr(sdf_grad), L.ptr(valid), L.ptr(part), L.stream()), "ia_eikonal")
+        L.lib().ia_eikonal(n, sdf_grad, valid, part)
         ctx.save_for_backward(sdf_grad, valid)
         return part
 
@@ -214,8 +190,7 @@ class _EikonalPartials(Function):
         sdf_grad, valid = ctx.saved_tensors
         out = torch.empty_like(sdf_grad)
         w = g_part.as_strided((1,), (1,))                     # d loss / d (sum): one scalar, whatever the view it arrived in
-        L.check(L.lib().ia_eikonal_bwd(L.i64(sdf_grad.shape[0]), L.ptr(sdf_grad), L.ptr(valid), L.ptr(w), L.ptr(out), L.stream()),
-                "ia_eikonal_bwd")
+        L.lib().ia_eikonal_bwd(sdf_grad.shape[0], sdf_grad, valid, w, out)
         return out, None
 
 
@@ -245,8 +220,7 @@ class _Alpha(Function):
         g = g.contiguous()
         g_sdf = torch.empty_like(sdf)
         g_beta = L.zeros(1, sdf.device)
-        L.check(L.lib().ia_laplace_alpha_bwd(L.i64(sdf.shape[0]), L.ptr(sdf), L.ptr(dists), L.f32(0.0), L.ptr(b), L.ptr(g),
-                                             L.ptr(g_sdf), L.ptr(g_beta), L.stream()), "ia_laplace_alpha_bwd")
+        L.lib().ia_laplace_alpha_bwd(sdf.shape[0], sdf, dists, 0.0, b, g, g_sdf, g_beta)
         return g_sdf, None, g_beta.reshape(())
 
 
@@ -278,17 +252,13 @@ class _Radiance(Function):
         ns, ptrs, strides, widths, muls, adds = _segs(segs)
         if FUSED_WGRAD:
             dW1, db1, dW2, db2, dW3, db3 = zeros_like_shapes([(64, 67), (64,), (64, 64), (64,), (3, 64), (3,)], dev)
-            L.check(L.lib().ia_mlp_bwd_fused(L.i32(1), L.i64(n), L.i32(ns), ptrs, strides, widths, muls, adds, L.ptr(W1k),
-                                             L.ptr(b1), L.ptr(W2), L.ptr(b2), L.ptr(W3), L.ptr(b3), L.ptr(g_rgb), L.ptr(g_x),
-                                             L.i32(68), L.ptr(dW1), L.ptr(db1), L.ptr(dW2), L.ptr(db2), L.ptr(dW3), L.ptr(db3),
-                                             L.stream()), "ia_mlp_bwd_fused")
+            L.lib().ia_mlp_bwd_fused(1, n, ns, ptrs, strides, widths, muls, adds, W1k, b1, W2, b2, W3, b3, g_rgb, g_x, 68, dW1, db1, dW2, db2, dW3,
+                                     db3)
         else:
             X = torch.empty((n, 68), device=dev)
             A1, A2, G1, G2 = (torch.empty((n, 64), device=dev) for _ in range(4))
             G3 = torch.empty((n, 16), device=dev)
-            L.check(L.lib().ia_mlp_bwd(L.i32(1), L.i64(n), L.i32(ns), ptrs, strides, widths, muls, adds, L.ptr(W1k), L.ptr(b1),
-                                       L.ptr(W2), L.ptr(b2), L.ptr(W3), L.ptr(b3), L.ptr(g_rgb), L.ptr(g_x), L.i32(68),
-                                       L.ptr(X), L.ptr(A1), L.ptr(A2), L.ptr(G1), L.ptr(G2), L.ptr(G3), L.stream()), "ia_mlp_bwd")
+            L.lib().ia_mlp_bwd(1, n, ns, ptrs, strides, widths, muls, adds, W1k, b1, W2, b2, W3, b3, g_rgb, g_x, 68, X, A1, A2, G1, G2, G3)
             dW1, db1 = wgrad(G1, 64, X, 67)
             dW2, db2 = wgrad(G2, 64, A1, 64)
             dW3, db3 = wgrad(G3, 3, A2, 64)
@@ -298,8 +268,7 @@ class _Radiance(Function):
         g_nw = g_x[:, 64:67]
         g_sh = g_x[:, 48:64]
         g_refl01 = torch.empty((n, 3), device=dev)
-        L.check(L.lib().ia_sh4_bwd(L.i64(n), L.ptr(refl01), C.c_void_p(g_sh.data_ptr()), L.i32(68), L.ptr(g_refl01),
-                                   L.stream()), "ia_sh4_bwd")
+        L.lib().ia_sh4_bwd(n, refl01, L.base_ptr(g_sh), 68, g_refl01)
         g_pos = None
         if ctx.needs_input_grad[0]:       # pose gradients: the hash Jacobian of grid #2 is recomputed here (not kept in forward)
             scale = ctx.scale

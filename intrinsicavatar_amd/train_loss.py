@@ -62,12 +62,10 @@ class _TrainLoss(Function):
         w = (C.c_float * N_TERMS)(*[float(x) for x in weights])
         terms, loss = torch.empty(N_TERMS, device=dev), torch.empty(1, device=dev)
         stats = torch.empty(N_STATS, dtype=torch.float64, device=dev)
-        k = int(L.lib().ia_train_loss_partials(L.i64(n), L.i64(m)))
+        k = int(L.lib().ia_train_loss_partials(n, m))
         partials = torch.empty(max(k, 1), dtype=torch.float64, device=dev)
-        L.check(L.lib().ia_train_loss(L.i64(n), L.i64(m), L.ptr(diff[0]), L.ptr(diff[1]), L.ptr(diff[2]), L.ptr(diff[3]), L.ptr(valid),
-                                      L.ptr(valid_phys), L.ptr(rgb), L.ptr(rgb_wo_mask), L.ptr(alpha), L.ptr(diff[4]), L.ptr(diff[5]),
-                                      L.ptr(diff[6]), L.ptr(diff[7]), L.ptr(sdf), L.ptr(sdf_grad), L.ptr(lap), w, L.f32(sparsity_scale),
-                                      L.ptr(terms), L.ptr(loss), L.ptr(stats), L.ptr(partials), L.stream()), "ia_train_loss")
+        L.lib().ia_train_loss(n, m, diff[0], diff[1], diff[2], diff[3], valid, valid_phys, rgb, rgb_wo_mask, alpha, diff[4], diff[5], diff[6],
+                              diff[7], sdf, sdf_grad, lap, w, sparsity_scale, terms, loss, stats, partials)
         ctx.save_for_backward(*[t for t in diff[:4] + [sdf, sdf_grad, lap, rgb, rgb_wo_mask, alpha, valid, valid_phys, stats] if t is not None])
         ctx.present = [t is not None for t in diff[:4] + [sdf, sdf_grad, lap, rgb, rgb_wo_mask, alpha, valid, valid_phys, stats]]
         ctx.cfg = (n, m, tuple(float(x) for x in weights), float(sparsity_scale), shapes, dev)
@@ -97,10 +95,8 @@ class _TrainLoss(Function):
             want = shapes[i] is not None and ctx.needs_input_grad[_N_CONST + i] and bool(live) and (name in _MAPS or inputs[name] is not None)
             grads.append(torch.empty(shapes[i], device=dev) if want else None)
         w = (C.c_float * N_TERMS)(*weights)
-        L.check(L.lib().ia_train_loss_bwd(L.i64(n), L.i64(m), L.ptr(rgb_full), L.ptr(phys_full), L.ptr(demod_full), L.ptr(opacity), L.ptr(valid),
-                                          L.ptr(valid_phys), L.ptr(rgb), L.ptr(rgb_wo_mask), L.ptr(alpha), L.ptr(sdf), L.ptr(sdf_grad),
-                                          L.ptr(lap), w, L.f32(sparsity_scale), L.ptr(stats), L.ptr(g_loss.reshape(1).float().contiguous()),
-                                          *[L.ptr(g) for g in grads], L.stream()), "ia_train_loss_bwd")
+        L.lib().ia_train_loss_bwd(n, m, rgb_full, phys_full, demod_full, opacity, valid, valid_phys, rgb, rgb_wo_mask, alpha, sdf, sdf_grad, lap, w,
+                                  sparsity_scale, stats, g_loss.reshape(1).float().contiguous(), *grads)
         return (None,) * _N_CONST + tuple(grads)
 
 

@@ -65,9 +65,8 @@ class _MLP2(Function):
         ns, ptrs, strides, widths, muls, adds = train._segs([(s, w, m, a) for s, (w, m, a) in zip(segs, ctx.spec)])
         shapes = [(64, in_dim), (64,), (64, 64), (64,), (ctx.out_dim, 64), (ctx.out_dim,)]
         d = train.zeros_like_shapes(shapes, dev)          # ONE fill for the six accumulated weight gradients
-        L.check(L.lib().ia_mlp_bwd_fused(L.i32(ctx.kind), L.i64(n), L.i32(ns), ptrs, strides, widths, muls, adds,
-                                         *[L.ptr(w) for w in ws], L.ptr(g_y.contiguous().float()), L.ptr(g_x), L.i32(pad),
-                                         *[L.ptr(t) for t in d], L.stream()), "ia_mlp_bwd_fused")
+        L.lib().ia_mlp_bwd_fused(ctx.kind, n, ns, ptrs, strides, widths, muls, adds, *ws, g_y.contiguous().float(), g_x, pad,
+                                 *d)
         g_segs, c0 = [], 0
         for k, (w, m, _) in enumerate(ctx.spec):
             if not ctx.needs_input_grad[8 + k]:          # e.g. the grid coordinates: constants of the step
@@ -88,9 +87,8 @@ class _MaterialAffine(Function):
         n, dev = mraw.shape[0], mraw.device
         alb, rgh, mtl = torch.empty((n, 3), device=dev), torch.empty((n, 1), device=dev), torch.empty((n, 1), device=dev)
         ctx.scales = (float(material.albedo_scale), float(material.roughness_scale), float(material.metallic_scale))
-        L.check(L.lib().ia_material_affine(L.i64(n), L.ptr(mraw), L.f32(material.albedo_scale), L.f32(material.albedo_bias),
-                                           L.f32(material.roughness_scale), L.f32(material.roughness_bias), L.f32(material.metallic_scale),
-                                           L.f32(material.metallic_bias), L.ptr(alb), L.ptr(rgh), L.ptr(mtl), L.stream()), "ia_material_affine")
+        L.lib().ia_material_affine(n, mraw, material.albedo_scale, material.albedo_bias, material.roughness_scale, material.roughness_bias,
+                                   material.metallic_scale, material.metallic_bias, alb, rgh, mtl)
         ctx.n = n
         ctx.dev = dev
         ctx.set_materialize_grads(False)
@@ -101,8 +99,7 @@ class _MaterialAffine(Function):
         cg = lambda t: t.contiguous() if t is not None else None      # noqa: E731
         g = torch.empty((ctx.n, 5), device=ctx.dev)
         a, r, m = ctx.scales
-        L.check(L.lib().ia_material_affine_bwd(L.i64(ctx.n), L.ptr(cg(g_alb)), L.ptr(cg(g_rgh)), L.ptr(cg(g_mtl)), L.f32(a), L.f32(r), L.f32(m),
-                                               L.ptr(g), L.stream()), "ia_material_affine_bwd")
+        L.lib().ia_material_affine_bwd(ctx.n, cg(g_alb), cg(g_rgh), cg(g_mtl), a, r, m, g)
         return g, None
 
 
@@ -118,11 +115,10 @@ class _PhysLoss(Function):
         n, dev = comp_rgb.shape[0], comp_rgb.device
         terms = torch.empty(5, device=dev)
         k = int(eik_part.shape[0]) if eik_part is not None else 0
-        nb = int(L.lib().ia_phys_loss_tmp_bytes(L.i64(n)))
+        nb = int(L.lib().ia_phys_loss_tmp_bytes(n))
         tmp = L.work_area(nb, dev) if nb else None
-        L.check(L.lib().ia_phys_loss(L.i64(n), L.ptr(comp_rgb), L.ptr(comp_rgb_phys), L.ptr(opacity), L.ptr(target_rgb), L.ptr(target_mask),
-                                     L.ptr(eik_part), L.i32(k), L.f32(lambda_phys), L.f32(lambda_mask), L.f32(lambda_eik), L.f32(eik_denom),
-                                     L.ptr(terms), L.ptr(tmp), L.stream()), "ia_phys_loss")
+        L.lib().ia_phys_loss(n, comp_rgb, comp_rgb_phys, opacity, target_rgb, target_mask, eik_part, k, lambda_phys, lambda_mask, lambda_eik,
+                             eik_denom, terms, tmp)
         ctx.save_for_backward(comp_rgb, comp_rgb_phys, opacity, target_rgb, target_mask)
         ctx.cfg = (float(lambda_phys), float(lambda_mask), float(lambda_eik), float(eik_denom), tuple(eik_part.shape) if eik_part is not None else None)
         ctx.mark_non_differentiable(terms)
@@ -138,9 +134,8 @@ class _PhysLoss(Function):
         g_phys = torch.empty_like(comp_rgb_phys) if comp_rgb_phys is not None else None
         g_op = torch.empty_like(opacity) if target_mask is not None else None
         g_eik = torch.empty(1, device=dev) if has_eik else None
-        L.check(L.lib().ia_phys_loss_bwd(L.i64(n), L.ptr(comp_rgb), L.ptr(comp_rgb_phys), L.ptr(opacity), L.ptr(target_rgb), L.ptr(target_mask),
-                                         L.ptr(g_loss.reshape(1).float().contiguous()), L.f32(lp), L.f32(lm), L.f32(le), L.f32(den),
-                                         L.ptr(g_rgb), L.ptr(g_phys), L.ptr(g_op), L.ptr(g_eik), L.stream()), "ia_phys_loss_bwd")
+        L.lib().ia_phys_loss_bwd(n, comp_rgb, comp_rgb_phys, opacity, target_rgb, target_mask, g_loss.reshape(1).float().contiguous(), lp, lm, le,
+                                 den, g_rgb, g_phys, g_op, g_eik)
         # (d loss / d eikonal sum is ONE scalar: it goes back as a stride-0 view of the partials' shape, train._EikonalPartials reads element 0)
         return g_rgb, g_phys, g_op, (g_eik.expand(has_eik) if has_eik else None), None, None, None, None, None, None
 

@@ -105,9 +105,11 @@ def _call_sites():
 
 def test_every_call_site_matches_the_header():
     """host logic: the loader takes argtypes / restype of all entry points from include/ia_amd.h; every call site in the package
-    must pass the declared NUMBER of arguments and, where the expression shows its ctypes class, the declared TYPE."""
+    must pass the declared NUMBER of arguments -- or one fewer where the last declared parameter is the stream, which the binding
+    then supplies -- and, where the expression shows its ctypes class, the declared TYPE."""
     from intrinsicavatar_amd import _lib
     protos = _lib.header_prototypes()
+    host_only = _lib.header_host_only()
     assert len(protos) == len(_declared_symbols())
     sites = _call_sites()
     assert len(sites) > 100
@@ -117,13 +119,47 @@ def test_every_call_site_matches_the_header():
             bad.append((f, line, name, "not declared in include/ia_amd.h"))
             continue
         want = protos[name][1]
-        if (not star and len(args) != len(want)) or (star and len(args) > len(want)):
+        counts = (len(want),) if name in host_only else (len(want) - 1, len(want))
+        if (not star and len(args) not in counts) or (star and len(args) > len(want)):
             bad.append((f, line, name, f"{len(args)} arguments, header declares {len(want)}"))
             continue
         if not star:
             for i, (k, w) in enumerate(zip(args, want)):
                 if k is not None and k is not w:
                     bad.append((f, line, name, f"argument {i}: {k.__name__} passed, header declares {w.__name__}"))
+    assert not bad, "\n".join(map(str, bad))
+
+
+def test_the_package_calls_entry_points_in_the_plain_form():
+    """inside the package a launch is `L.lib().ia_name(tensors and numbers)`: the binding marshals, supplies the stream and checks
+    the status.  The wrapped form (L.check / L.i64 / L.i32 / L.f32 / L.ptr / L.stream) is for bench.py, tools/ and the tests."""
+    import ast
+    pkg = os.path.join(ROOT, "intrinsicavatar_amd")
+    wrapped = {"check", "i64", "i32", "f32", "ptr", "stream"}
+
+    def is_wrapper(n):
+        return (isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr in wrapped
+                and isinstance(n.func.value, ast.Name) and n.func.value.id == "L")
+
+    bad, n_sites = [], 0
+    for f in sorted(os.listdir(pkg)):
+        if not f.endswith(".py") or f == "_lib.py":
+            continue
+        src = open(os.path.join(pkg, f)).read()
+        for spelling in ("L.check(", "L.i64(", "L.i32(", "L.f32(", "L.stream()"):
+            if spelling in src:
+                bad.append((f, spelling))
+        tree = ast.parse(src)
+        for node in ast.walk(tree):
+            if is_wrapper(node) and any(isinstance(m, ast.Attribute) and m.attr.startswith("ia_") for m in ast.walk(node)):
+                bad.append((f, node.lineno, "an ia_* call inside L." + node.func.attr))
+            if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr.startswith("ia_"):
+                n_sites += 1
+                if ast.unparse(node.func.value) != "L.lib()":
+                    bad.append((f, node.lineno, node.func.attr, "not spelled L.lib().ia_*"))
+                bad += [(f, m.lineno, node.func.attr, "L." + m.func.attr + " in its arguments")
+                        for a in node.args for m in ast.walk(a) if is_wrapper(m)]
+    assert n_sites > 100
     assert not bad, "\n".join(map(str, bad))
 
 

@@ -415,3 +415,26 @@ def test_small_batches_search_all_inits_side_by_side_with_the_same_candidates(ma
     # the SDF-only product call on a small batch = the rows of the full batch
     s_full = dfm.deform_sdf(pts[:300_000].contiguous(), rs.geometry)
     assert torch.equal(dfm.deform_sdf(pts[:40_000].contiguous(), rs.geometry), s_full[:40_000])
+
+
+def test_timing_extras_are_the_optional_outputs_the_search_was_called_with(march):
+    """bench.py's bytes model reads I / J_inv / fwd_J of every search launch from the binding's timing table: they are what the call
+    passed, whether the arguments are tensors (the package) or wrapped pointers."""
+    from intrinsicavatar_amd import _lib as L, fast_snarf
+    SP, rs, pts, _ = march
+    dfm = rs.deformer
+    sub = pts[:257].contiguous()
+    P, I = sub.shape[0], dfm.init_bones.shape[0]
+    lib = L.lib()
+    lib.start()
+    try:
+        dfm.search(sub, want_fwd=True)                                       # the package's own call: fwd_J, no J_inv
+        x, v = torch.zeros((1, P, I, 3), device=DEV), torch.zeros((1, P, I), dtype=torch.bool, device=DEV)
+        Ji = torch.zeros((1, P, I, 3, 3), device=DEV)
+        fast_snarf.fuse_broyden_spec(x, sub[None], fast_snarf.ChannelLastVoxelJ(dfm.voxel_J_cl), dfm.tfs, dfm.init_bones, Ji, v,
+                                     dfm.offset_kernel, dfm.scale_kernel, 1e-5, 1e-1, 1e-3)          # J_inv, no fwd_J
+    finally:
+        rep = lib.report(detail=True)
+    calls = [(k, u, e) for k, rows in rep.items() if k.startswith("ia_fuse_broyden") for _, u, e in rows]
+    assert len(calls) == 2 and all(u == P for _, u, _ in calls), calls
+    assert sorted((e["I"], e["J_inv"], e["fwd_J"]) for _, _, e in calls) == [(I, False, True), (I, True, False)], calls

@@ -293,3 +293,32 @@ def test_ray_transform_kernel_is_the_library_product_bit_for_bit():
     nn = np.linalg.norm(on, axis=-1, keepdims=True)
     ref = np.concatenate([on, rn[:, 3:6] @ wn[:3, :3].T, nn - 1, nn + 1], 1).astype(np.float32)
     assert np.array_equal(out.cpu().numpy(), ref)
+
+
+def test_plain_and_wrapped_call_forms_are_the_same_launch():
+    """one callable per entry point takes both spellings: tensors and numbers with the stream left out (the package), and the
+    wrapped arguments with an explicit stream inside L.check (bench.py, tools/).  ia_ray_points at n = 0 (returns before any launch),
+    1 and 65 (one wave plus one lane): outputs bit-identical, and the timing table lists every call with units = n, no extras."""
+    from intrinsicavatar_amd import _lib as L
+    lib = L.lib()
+    g = torch.Generator().manual_seed(5)
+    ro, rd = torch.randn((7, 3), generator=g).to(DEV), torch.randn((7, 3), generator=g).to(DEV)
+    sizes, outs = (0, 1, 65), []
+    lib.start()
+    try:
+        for n in sizes:
+            ri = torch.randint(0, 7, (n,), generator=g).to(DEV)
+            t0 = torch.rand(n, generator=g).to(DEV)
+            t1 = t0 + 0.25
+            a, b = torch.full((n, 3), math.nan, device=DEV), torch.full((n, 3), math.nan, device=DEV)
+            assert lib.ia_ray_points(n, ro, rd, ri, t0, t1, a) == 0
+            L.check(lib.ia_ray_points(L.i64(n), L.ptr(ro), L.ptr(rd), L.ptr(ri), L.ptr(t0), L.ptr(t1), L.ptr(b), L.stream()), "ia_ray_points")
+            outs.append((a, b, ro[ri] + rd[ri] * ((t0 + t1) * 0.5)[:, None]))
+    finally:
+        rep = lib.report(detail=True)
+    assert [(u, x) for _, u, x in rep["ia_ray_points"]] == [(n, None) for n in sizes for _ in range(2)]
+    for a, b, want in outs:
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32)) and not bool(torch.isnan(a).any())
+        _close(a, want, 1e-6, 1e-6, "ray_points")
+    with pytest.raises(L.IaError, match="need GPU tensors"):
+        lib.ia_ray_points(1, ro.cpu(), rd, ri, t0, t1, a)

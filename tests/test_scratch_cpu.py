@@ -64,7 +64,7 @@ def test_sizes_stay_within_the_footprint_bound(size_rows):
 
 
 def test_untimed_entry_points_are_the_stream_less_prototypes():
-    """_Timed wraps an entry point in events iff it can launch work, i.e. iff its prototype takes an ia_stream_t"""
+    """the binding wraps an entry point (stream, status, events) iff it can launch work, i.e. iff its prototype takes an ia_stream_t"""
     from intrinsicavatar_amd import _lib, build
     hdr = open(os.path.join(ROOT, "include", "ia_amd.h")).read()
     hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
