@@ -860,6 +860,35 @@ int64_t ia_metric_ssim_tmp_bytes(int H, int W, int C);
 int ia_metric_ssim(int H, int W, int C, const float* a, const float* b, const int32_t* rect, void* tmp, double* out, ia_stream_t stream);
 
 /* ------------------------------------------------------------------------- */
+/* LPIPS (csrc/lpips.hip): systems/criterions.py:105-126 with lpips.LPIPS(net="vgg") -- the VGG-16 trunk in f32, NHWC, and the feature
+ * distance of its five taps.  Activations are the caller's buffers, sized for the FULL frame: a buffer of level l is [N, H >> l, W >> l, C].
+ * rect [4] int32 = (x, y, w, h) ON THE DEVICE (ia_metric_mask_rect's output; NULL = the whole buffer): a kernel of level l works on the
+ * extent (h >> l) x (w >> l) at the buffer's origin, workgroups outside it exit, and nothing outside it is read -- so a call with a
+ * rectangle gives the bits of a call on the cropped images.  H, W are always the dimensions of the buffer that is READ.
+ *
+ * ia_lpips_pixels_per_partial: pixels that one partial sum of ia_lpips_layer_dist covers.
+ * ia_lpips_input: img [N,H,W,3] in [0,1] -> out [N,H,W,4]: the rectangle moved to the origin, 2x - 1 when normalize, then
+ *   (x - shift) / scale with shift (-.030, -.088, -.188), scale (.458, .448, .450); channel 3 = 0.
+ * ia_lpips_conv3x3: out [N,H,W,Cout] = relu(conv3x3(in [N,H,W,Cin], pad 1, stride 1) + bias); wpk [9,Cin,Cout] (tap = 3 ky + kx), Cin a
+ *   multiple of 4, Cout of 64.  Implicit GEMM on v_mfma_f32_32x32x2_f32: exact f32, one k-ordered fmaf chain per output, the same for
+ *   every pixel.  The halo outside the extent is zero.  at_rect = 1 (level 0 only): the window is read at the rectangle's corner (x, y)
+ *   instead of the origin; the result is written at the origin either way.
+ * ia_lpips_maxpool2: in [N,H,W,C] of `level` -> out [N,H >> 1,W >> 1,C], 2 x 2 / stride 2 / floor; C a multiple of 4.
+ * ia_lpips_layer_dist: f0, f1 [N,H,W,C] of `level`, lin [C] -> partials [N,cap] fp64: per pixel sum_c lin[c] (f0_c / (|f0| + 1e-10) -
+ *   f1_c / (|f1| + 1e-10))^2, ia_lpips_pixels_per_partial() consecutive pixels OF THE EXTENT per partial; cap >= ceil(H W / that).
+ * ia_lpips_finish: H, W of level 0; partials [5,N,cap] of the five taps -> out [N + 1] fp32 = per image sum_l mean over the extent of
+ *   level l (fp64, fixed order, no atomics), then the status: 0, 2 = rectangle not inside the image, 3 = a side of the rectangle < 16
+ *   (nothing left at the fifth tap; an empty mask); the values are NaN then. */
+int ia_lpips_pixels_per_partial(void);
+int ia_lpips_input(int64_t N, int H, int W, const float* img, const int32_t* rect, int normalize, float* out, ia_stream_t stream);
+int ia_lpips_conv3x3(int64_t N, int H, int W, int Cin, int Cout, const float* in, const float* wpk, const float* bias, float* out,
+                     const int32_t* rect, int level, int at_rect, ia_stream_t stream);
+int ia_lpips_maxpool2(int64_t N, int H, int W, int C, const float* in, float* out, const int32_t* rect, int level, ia_stream_t stream);
+int ia_lpips_layer_dist(int64_t N, int H, int W, int C, const float* f0, const float* f1, const float* lin, const int32_t* rect, int level,
+                        double* partials, int64_t cap, ia_stream_t stream);
+int ia_lpips_finish(int64_t N, int H, int W, const int32_t* rect, const double* partials, int64_t cap, float* out, ia_stream_t stream);
+
+/* ------------------------------------------------------------------------- */
 /* Deformer construction (csrc/skinning.hip): ForwardDeformer.switch_to_explicit(use_smpl=True) + query_weights_smpl
  * (models/deformers/fast_snarf/deformer_torch.py:139-253) on the device.  Conventions (voxel order, tie rule, summation orders):
  * csrc/skin_math.h and DESIGN.md "Deformer construction".  None of the four needs scratch memory.

@@ -40,6 +40,7 @@ SOURCES = {
     "lbs_fwd.hip": ["-ffp-contract=off"],
     "mesh_attr.hip": ["-ffp-contract=off"],
     "train_loss.hip": ["-ffp-contract=off"],
+    "lpips.hip": ["-ffp-contract=off"],
 }
 
 

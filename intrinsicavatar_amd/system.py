@@ -7,7 +7,8 @@
     model_forward     models/intrinsic_avatar.py:1653-1666  IntrinsicAvatarModel.forward: forward_ as it is in training, chunk_batch over
                                                             `ray_chunk` rays with the results moved to the host in evaluation, + "beta"
     evaluate_frame    systems/intrinsic_avatar.py:317-421,  the numeric part of validation_step / test_step: albedo-only pass -> ratio ->
-                      :597-720                              relit pass, and the frame's metrics (metrics.py: kernels, results on the device)
+                      :597-720                              relit pass, and the frame's metrics (metrics.py: kernels, results on the device;
+                                                            the three *_lpips values on request, lpips=<metrics.LPIPSNet>)
     evaluate_sequence systems/intrinsic_avatar.py:597-720,  `mode=test` over a split with ground truth (data.TruthFrames): per frame the
                       models/intrinsic_avatar.py:281-305    pose / occupancy grid / emitter of `prepare`, then evaluate_frame
     mean_metrics      systems/intrinsic_avatar.py:869-911   test_epoch_end: the mean of every metric over the frames, one read-back
@@ -114,16 +115,20 @@ def model_forward(rs, rays: Tensor, material, emitter, spp: int, light_u: Tensor
 
 
 METRIC_KEYS = ("rf_psnr", "rf_ssim", "normal_error", "pbr_psnr", "pbr_ssim", "albedo_psnr", "albedo_ssim")      # the reference's, minus *_lpips
+LPIPS_KEYS = ("rf_lpips", "pbr_lpips", "albedo_lpips")                # ... which a call with lpips=<metrics.LPIPSNet> adds
 
 
 def evaluate_frame(rs, batch: Dict[str, Tensor], material, emitter, spp: int, light_u: Tensor, shuffle_u: Optional[Tensor] = None, *,
-                   img_wh: Tuple[int, int], stage: str = "test", **kw) -> Tuple[Dict[str, Tensor], Dict[str, Tensor]]:
+                   img_wh: Tuple[int, int], stage: str = "test", lpips=None, **kw) -> Tuple[Dict[str, Tensor], Dict[str, Tensor]]:
     """the numeric part of validation_step (:317-421) / test_step (:597-720) on a batch that went through preprocess_data (device
     tensors).  stage "test" with both "hdri" and "albedo" in the batch: an albedo-only pass, the per-channel ratio against the ground
     truth, then the full pass with that ratio (its comp_albedo_full IS the aligned albedo, :697-698); otherwise one full pass and, if
     "albedo" is there, the alignment afterwards (:380-399, :681-696).  -> (metrics, out): metrics under the reference's keys without
     *_lpips, 0-d device tensors (metrics.to_host(metrics): every one of them with a single read-back); out = the model's dict on the
-    device with "comp_normal" in OpenGL camera space, + "aligned_albedo" when one was formed.  **kw goes to model_forward."""
+    device with "comp_normal" in OpenGL camera space, + "aligned_albedo" when one was formed.  lpips: a metrics.LPIPSNet adds the
+    reference's rf_lpips / pbr_lpips (valid_mask's rectangle) and albedo_lpips (gt_mask's), each under the condition of the SSIM next to
+    it and equal to metrics.LPIPS()(prediction, target, lpips, valid_mask) bit for bit; five images go through the trunk, in two
+    batches.  **kw goes to model_forward."""
     assert stage in ("validation", "test")
     W, H = img_wh
     rays = batch["rays"]
@@ -144,6 +149,10 @@ def evaluate_frame(rs, batch: Dict[str, Tensor], material, emitter, spp: int, li
         rect = metrics.mask_rect(valid.reshape(H, W)) if valid is not None else None
         ret["rf_psnr"] = psnr(out["comp_rgb_full"], batch["rgb"], valid_mask=valid)
         ret["rf_ssim"] = metrics.ssim(img(out["comp_rgb_full"]), img(batch["rgb"]), rect)
+        if lpips is not None:
+            # (one batch of three through the trunk: the target once, and three times the workgroups in the deep layers)
+            feats = metrics.lpips_features(lpips, [img(out["comp_rgb_full"]), img(out["comp_rgb_phys_full"]), img(batch["rgb"])], rect)
+            ret["rf_lpips"] = metrics.lpips_of_features(lpips, feats, feats, rect, slots=(0, 2))
     if "normal" in batch:
         r = metrics.normal_error(out["comp_normal"], batch["normal"], gt_mask, w2c=batch.get("w2c"), transform=True, normalize=True,
                                  want_camera=True)
@@ -154,6 +163,8 @@ def evaluate_frame(rs, batch: Dict[str, Tensor], material, emitter, spp: int, li
     if "rgb" in batch:
         ret["pbr_psnr"] = psnr(out["comp_rgb_phys_full"], batch["rgb"], valid_mask=valid)
         ret["pbr_ssim"] = metrics.ssim(img(out["comp_rgb_phys_full"]), img(batch["rgb"]), rect)
+        if lpips is not None:
+            ret["pbr_lpips"] = metrics.lpips_of_features(lpips, feats, feats, rect, slots=(1, 2))
     if "albedo" in batch:
         if aligned_by_model:
             aligned = out["comp_albedo_full"]
@@ -162,19 +173,23 @@ def evaluate_frame(rs, batch: Dict[str, Tensor], material, emitter, spp: int, li
         out["aligned_albedo"] = aligned
         ret["albedo_psnr"] = psnr(aligned, gt_albedo, valid_mask=gt_mask)
         ret["albedo_ssim"] = ssim(img(aligned), img(gt_albedo), valid_mask=gt_mask.reshape(H, W))
+        if lpips is not None:
+            grect = metrics.mask_rect(gt_mask.reshape(H, W))
+            feats = metrics.lpips_features(lpips, [img(aligned), img(gt_albedo)], grect)
+            ret["albedo_lpips"] = metrics.lpips_of_features(lpips, feats, feats, grect, slots=(0, 1))
     return ret, out
 
 
 def evaluate_sequence(rs, material, frames, body, spp: int, *, stage: str = "test", emitter=None, render_mode: str = "light",
                       global_illumination: bool = True, resample_light: bool = True, generator: Optional[torch.Generator] = None,
                       frames_idx: Optional[Iterable[int]] = None, cano_pose="da_pose", occ_res: int = 64,
-                      ray_chunk: int = 1 << 19) -> Iterator[Tuple[int, Dict[str, Tensor], Dict[str, Tensor]]]:
+                      ray_chunk: int = 1 << 19, lpips=None) -> Iterator[Tuple[int, Dict[str, Tensor], Dict[str, Tensor]]]:
     """the reference's `mode=test` over a split with ground truth: yields (idx, metrics, out) per frame of data.TruthFrames -- full_frame
     -> animation.prepare_frame (pose, bbox, test occupancy grid, as render_sequence) -> preprocess_data(stage) -> evaluate_frame with
     img_wh = frames.img_wh.  `out` also carries the random tensors it was made with (`light_u`, `shuffle_u`), drawn from `generator` in
     render_sequence's order.  emitter: given, or an EnvironmentLightTensor of the frame's "hdri", rebuilt (with update_pdf) only when
     that tensor changes (IntrinsicAvatarModel.prepare, models/intrinsic_avatar.py:286-305); resample_light=False draws light_u once.
-    mean_metrics(list of the yielded metrics) is test_epoch_end."""
+    lpips: a metrics.LPIPSNet for the three *_lpips values (evaluate_frame).  mean_metrics(list of the yielded metrics) is test_epoch_end."""
     from . import animation, smpl                                   # (animation imports this module)
     if render_mode in ("mats", "mis"):
         raise NotImplementedError("evaluate_sequence draws the random tensors of the light / uniform_light estimators")
@@ -204,7 +219,7 @@ def evaluate_sequence(rs, material, frames, body, spp: int, *, stage: str = "tes
             light_u = animation._rand((n_light, 3), dev, generator)
         shuffle_u = animation._rand((rays.shape[0], spp), dev, generator)
         ret, out = evaluate_frame(rs, batch, material, emitter, spp, light_u, shuffle_u, img_wh=frames.img_wh, stage=stage, background_color=bg,
-                                  global_illumination=global_illumination, render_mode=render_mode, ray_chunk=ray_chunk)
+                                  global_illumination=global_illumination, render_mode=render_mode, ray_chunk=ray_chunk, lpips=lpips)
         out["light_u"], out["shuffle_u"] = light_u, shuffle_u
         yield int(idx), ret, out
 
