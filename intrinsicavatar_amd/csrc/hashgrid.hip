@@ -454,8 +454,8 @@ __global__ __launch_bounds__(THREADS) void hash_bwd_runs_kernel(int64_t n, const
 // ~21 G atomics/s measured on MI355X), so the scatter above is pinned at n*L*8*2 atomics no matter how it is
 // scheduled.  This path issues (almost) none.  The table of every level is cut into slices of 8192 entries (64 KB of
 // float2 -- one LDS-resident accumulator per workgroup); a "bucket" is one (level, slice):
-//   1. count : per workgroup (1024 points) an LDS histogram of its records per bucket -> counts[bucket][wg]
-//   2. scan  : exclusive scan of that matrix in bucket-major order = the base of every (bucket, wg) run
+//   1. count : per unit (one wave, 128 points) an LDS histogram of its records per bucket -> counts[bucket][unit]
+//   2. scan  : exclusive scan of that matrix in bucket-major order = the base of every (bucket, unit) run
 //   3. fill  : records (13-bit local index as u16, float2 value) are written to their run (wave-level run merging
 //              first: consecutive samples of a ray falling into the same cell become one record)
 //   4. reduce: one workgroup per (bucket, part) streams its records (coalesced 10 B / record), accumulates them
@@ -464,8 +464,6 @@ __global__ __launch_bounds__(THREADS) void hash_bwd_runs_kernel(int64_t n, const
 // HBM traffic ~ 2 x 10 B per record instead of 2 fabric atomics per record.
 constexpr int SLICE_LOG2 = 13;
 constexpr int SLICE = 1 << SLICE_LOG2;
-constexpr int BIN_ROUNDS = 4;
-constexpr int BIN_TILE = THREADS * BIN_ROUNDS;      // points per workgroup
 constexpr int MAX_BUCKETS = 1024;
 constexpr int MAX_PARTS = 64;
 constexpr int PART_RECORDS = 1 << 19;
@@ -496,138 +494,10 @@ __device__ __forceinline__ void level_max_update(unsigned* p, float lmax)
     if (v > __atomic_load_n(p, __ATOMIC_RELAXED)) atomicMax(p, v);
 }
 
-template <bool SECOND, bool FILL>
-__global__ __launch_bounds__(THREADS) void hash_bin_kernel(int64_t n, const float* __restrict__ x, HashCfg cfg, BinCfg bins,
-                                                            const float* __restrict__ gE, int gE_stride,
-                                                            const float* __restrict__ gG, int gG_stride,
-                                                            const float* __restrict__ q, int nwg,
-                                                            int32_t* __restrict__ counts, uint16_t* __restrict__ rec_idx,
-                                                            float2* __restrict__ rec_val, uint32_t level_mask,
-                                                            unsigned* __restrict__ level_max)
-{
-    // Loop order: level-major over the workgroup's 1024 points (4 per lane), so that at any time a workgroup appends to
-    // the <= 64 runs of ONE level only (64 x 2 open cache lines instead of 771 x 2): the scattered 2- and 8-byte record
-    // stores then merge in L2 into full lines before they are evicted to HBM.  Gradient rows are fetched 4 levels at a
-    // time (one 32-byte piece per point and array), positions once.
-    __shared__ int hist[MAX_BUCKETS];
-    __shared__ int base[FILL ? MAX_BUCKETS : 1];
-    const int lane = threadIdx.x & 63;
-    for (int b = threadIdx.x; b < bins.n_buckets; b += THREADS) {
-        hist[b] = 0;
-        if (FILL) base[b] = counts[(int64_t)b * nwg + blockIdx.x];
-    }
-    __syncthreads();
-    float px[BIN_ROUNDS][3], pq[BIN_ROUNDS][3];
-    bool act[BIN_ROUNDS];
-    int64_t pi[BIN_ROUNDS];
-#pragma unroll
-    for (int r = 0; r < BIN_ROUNDS; r++) {
-        const int64_t i = (int64_t)blockIdx.x * BIN_TILE + r * THREADS + threadIdx.x;
-        act[r] = i < n;
-        pi[r] = act[r] ? i : n - 1;
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            px[r][d] = x[pi[r] * 3 + d];
-            pq[r][d] = (SECOND && FILL) ? q[pi[r] * 3 + d] : 0.0f;
-        }
-    }
-    constexpr int LG = 4;                                     // levels per gradient fetch
-    for (int l0 = 0; l0 < cfg.n_levels; l0 += LG) {
-        float2 ev[BIN_ROUNDS][LG], gv[BIN_ROUNDS][LG];
-#pragma unroll
-        for (int r = 0; r < BIN_ROUNDS; r++)
-#pragma unroll
-            for (int j = 0; j < LG; j++) {
-                ev[r][j] = make_float2(0.f, 0.f);
-                gv[r][j] = make_float2(0.f, 0.f);
-                if (FILL && act[r] && l0 + j < cfg.n_levels && ((level_mask >> (l0 + j)) & 1u)) {
-                    if (gE) ev[r][j] = *reinterpret_cast<const float2*>(gE + pi[r] * gE_stride + (l0 + j) * 2);
-                    if (SECOND) gv[r][j] = *reinterpret_cast<const float2*>(gG + pi[r] * gG_stride + (l0 + j) * 2);
-                }
-            }
-#pragma unroll
-        for (int j = 0; j < LG; j++) {
-            const int l = l0 + j;
-            if (l >= cfg.n_levels) break;
-            if (!((level_mask >> l) & 1u)) continue;              // level switched off by the caller (progressive bands)
-            float lmax = 0.0f;
-            const float sc = cfg.scale[l];
-            const uint32_t res = cfg.res[l], hsize = cfg.offsets[l + 1] - cfg.offsets[l];
-            const int b0 = bins.bstart[l];
-#pragma unroll
-            for (int r = 0; r < BIN_ROUNDS; r++) {
-                const float2 e = ev[r][j], g = gv[r][j];
-                const bool active = act[r];
-                float pos[3];
-                uint32_t pg[3];
-#pragma unroll
-                for (int d = 0; d < 3; d++) {
-                    const float p = fmaf(sc, px[r][d], 0.5f);
-                    const float fl = floorf(p);
-                    pg[d] = (uint32_t)(int)fl;
-                    pos[d] = p - fl;
-                }
-#pragma unroll
-                for (int c = 0; c < 8; c++) {
-                    uint32_t idx = grid_index(hsize, res, pg[0] + (c & 1), pg[1] + ((c >> 1) & 1), pg[2] + ((c >> 2) & 1));
-                    if (!active) idx = 0xFFFFFFFFu;
-                    const uint32_t prev = __shfl_up(idx, 1, 64);
-                    const bool head = (lane == 0) || (prev != idx);
-                    const unsigned long long heads = __ballot(head);
-                    const bool tail = (lane == 63) || ((heads >> (lane + 1)) & 1ull);
-                    float vx = 0.f, vy = 0.f;
-                    if (FILL) {
-                        const float wx = (c & 1) ? pos[0] : 1.0f - pos[0];
-                        const float wy = (c & 2) ? pos[1] : 1.0f - pos[1];
-                        const float wz = (c & 4) ? pos[2] : 1.0f - pos[2];
-                        const float w0 = wx * wy * wz;
-                        vx = e.x * w0; vy = e.y * w0;
-                        if (SECOND) {
-                            const float dw = ((c & 1) ? sc : -sc) * wy * wz * pq[r][0] + ((c & 2) ? sc : -sc) * wx * wz * pq[r][1] +
-                                             ((c & 4) ? sc : -sc) * wx * wy * pq[r][2];
-                            vx += g.x * dw;
-                            vy += g.y * dw;
-                        }
-                        if (!active) { vx = 0.f; vy = 0.f; }
-                        const unsigned long long below = heads & ((lane == 63) ? ~0ull : ((1ull << (lane + 1)) - 1ull));
-                        const int hpos = 63 - __clzll(below);
-                        if (heads != ~0ull) {                           // wave-uniform: some run is longer than one lane
-#pragma unroll
-                            for (int off = 1; off < 64; off <<= 1) {
-                                const float ax = __shfl_up(vx, off, 64), ay = __shfl_up(vy, off, 64);
-                                if (lane - off >= hpos) { vx += ax; vy += ay; }
-                            }
-                        }
-                    }
-                    if (tail && active) {
-                        const int b = b0 + (int)(idx >> SLICE_LOG2);
-                        const int rank = atomicAdd(&hist[b], 1);
-                        if (FILL) {
-                            lmax = fmaxf(lmax, fmaxf(fabsf(vx), fabsf(vy)));
-                            const int64_t p = (int64_t)base[b] + rank;
-                            rec_idx[p] = (uint16_t)(idx & (SLICE - 1));
-                            rec_val[p] = make_float2(vx, vy);
-                        }
-                    }
-                }
-            }
-            if (FILL) {                                           // per-level max |value| -> fixed-point scale of the reduction
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) lmax = fmaxf(lmax, __shfl_xor(lmax, off, 64));
-                if (lane == 0 && lmax > 0.0f) level_max_update(level_max + l, lmax);
-            }
-        }
-    }
-    if (!FILL) {
-        __syncthreads();
-        for (int b = threadIdx.x; b < bins.n_buckets; b += THREADS) counts[(int64_t)b * nwg + blockIdx.x] = hist[b];
-    }
-}
-
-
-// ---- binned backward, STAGED variant: wave-private units and full-line record stores ---------------------------------
-// The fill above appends every record straight to its (bucket, workgroup) run: a wave's store instruction scatters 64
-// lanes over up to 64 runs (PMC: 6.7 GB written + 3-6 GB write-allocated for 4.2 GB of records).  Here the unit of the
+// ---- binned backward, count and STAGED fill: wave-private units and full-line record stores ------------------------
+// The first fill (direct, per workgroup of 1024 points; retired: tools/experiments/retired_ab_variants.patch) appended every
+// record straight to its (bucket, workgroup) run: a wave's store instruction scattered 64 lanes over up to 64 runs (PMC:
+// 6.7 GB written + 3-6 GB write-allocated for 4.2 GB of records; 1.8 x slower).  Here the unit of the
 // count -> scan -> fill protocol is ONE WAVE (128 points): per level the wave sorts its <= 1024 records by slice in a
 // 10 KB LDS staging area (offsets come from the scanned counts, positions from integer LDS atomics), then copies the
 // sorted block out so that consecutive lanes write consecutive records of a run.  No workgroup barrier anywhere: waves
@@ -1150,7 +1020,6 @@ IA_EXPORT int ia_hashgrid_fwd_xcd(int64_t n, const float* x, const float* params
         //  6 -> 21.0, 7 -> 20.9; headline step 116.3 / 113.5 / 113.9 ms for 5 / 6 / 7)
         chunks_plain = (b0 > 6 ? 6 : (b0 > 0 ? b0 : 4)) * per_xcd;
         chunks_jac = (b1 > 6 ? 6 : (b1 > 0 ? b1 : 4)) * per_xcd;
-        if (const char* e = getenv("IA_HASH_XCD_CHUNKS")) chunks_plain = chunks_jac = atoi(e);
     }
     const int chunks = dy_dx ? chunks_jac : chunks_plain;
     int l = n_small;
@@ -1165,16 +1034,15 @@ IA_EXPORT int ia_hashgrid_fwd_xcd(int64_t n, const float* x, const float* params
     // 140 k points 0.184 / 0.101, 206 k 0.223 / 0.147, 557 k 0.287 / 0.335, 1 M 0.445 / 0.581, 10 M 2.19 / 3.02).
     static const int plan_env = getenv("IA_HASH_XCD_PLAN") ? (getenv("IA_HASH_XCD_PLAN")[0] == 'p' ? 1 : 2) : 0;      // 1: passes, 2: by level, 0: by size
     const bool by_level = plan_env == 2 || (plan_env == 0 && n >= 300000);
-    // experiment knob (round 5): hashed levels per launch (default 1).  Two levels per launch read the coordinates half as often and put
-    // 8 MB of tables in front of every XCD's 4 MB L2 -- measured: DESIGN 4.3.
-    static const int lpl = getenv("IA_HASH_LEVELS_PER_LAUNCH") ? max(1, atoi(getenv("IA_HASH_LEVELS_PER_LAUNCH"))) : 1;
+    // One hashed level per launch.  Two / three levels per launch (round 5) read the coordinates half / a third as often and put
+    // 8 / 12 MB of tables in front of every XCD's 4 MB L2: 5 % / 12 % slower; retired.
     if (by_level) {
-        for (int u = (n_small > 0 ? -1 : 0); u < n_levels - n_small; u += (u < 0 ? 1 : lpl)) {
+        for (int u = (n_small > 0 ? -1 : 0); u < n_levels - n_small; u++) {
             XcdPlan plan;
             plan.straight = 1;
             for (int k = 0; k < 8; k++) {
                 plan.first_level[k] = u < 0 ? 0 : n_small + u;
-                plan.n_level[k] = u < 0 ? n_small : min(lpl, n_levels - n_small - u);
+                plan.n_level[k] = u < 0 ? n_small : 1;
                 plan.part[k] = k; plan.nparts[k] = 8;
             }
             if (dy_dx) hash_fwd_xcd_kernel<true><<<8 * chunks, THREADS, 0, s>>>(n, x, (const float2*)params, c, plan, tmp, tmp_jac);
@@ -1196,7 +1064,7 @@ IA_EXPORT int ia_hashgrid_fwd_xcd(int64_t n, const float* x, const float* params
             // sorted points, so the whole small set costs about as much as ONE hashed level -- weighing it by its level count (5)
             // left three XCDs with a full hashed level each while five XCDs idled through a fifth of the small set.
             const int units = big_left + (small_done ? 0 : 1);
-            static const float small_cost = getenv("IA_HASH_SMALL_COST") ? (float)atof(getenv("IA_HASH_SMALL_COST")) : 1.0f;
+            const float small_cost = 1.0f;
             float w[9];
             int share[9], used = 0;
             for (int u = 0; u < units; u++) { w[u] = (!small_done && u == units - 1) ? small_cost : 1.0f; share[u] = 1; used++; }
@@ -1282,19 +1150,9 @@ struct BinLayout {
     uint16_t* rec_idx;
     bool fits;
 };
-bool staged_fill()
-{
-    static int mode = -1;
-    if (mode < 0) {
-        const char* e = getenv("IA_HASHBWD_FILL");        // test hook: "direct" = per-workgroup runs, scattered appends
-        mode = (e && e[0] == 'd') ? 0 : 1;
-    }
-    return mode == 1;
-}
-
 size_t bin_layout(void* scratch, size_t bytes, int64_t n, int n_levels, int n_buckets, BinLayout* L)
 {
-    L->nwg = staged_fill() ? ia::cdiv(n, U_PTS) : ia::cdiv(n, BIN_TILE);       // units of the count matrix
+    L->nwg = ia::cdiv(n, U_PTS);       // units of the count matrix
     L->m = (int64_t)n_buckets * L->nwg;
     L->records = n * n_levels * 8;
     ia::Carver c(scratch, bytes);
@@ -1349,32 +1207,21 @@ IA_EXPORT int ia_hashgrid_bwd_binned(int64_t n, const float* x, int n_levels, in
     hipStream_t s = (hipStream_t)stream;
     unsigned* level_max = L.level_max;
     if (hipMemsetAsync(level_max, 0, MAX_LEVELS * sizeof(unsigned), s) != hipSuccess) return ia::check_launch("ia_hashgrid_bwd_binned(memset)");
-    const bool staged = staged_fill();
     const int ugrid = ia::cdiv(L.nwg, U_WAVES);
     constexpr size_t lds_count = (size_t)U_WAVES * MAX_BUCKETS * sizeof(int), lds_fill = (size_t)U_WAVES * sizeof(UnitLds);
-    if (staged) {
-        if (g_jac) hash_bin_unit_kernel<true, false><<<ugrid, THREADS, lds_count, s>>>(n, x, c, b, g_enc, g_enc_stride, g_jac, g_jac_stride, q, L.nwg, L.m, counts, total, rec_idx, rec_val, level_mask, level_max);
-        else hash_bin_unit_kernel<false, false><<<ugrid, THREADS, lds_count, s>>>(n, x, c, b, g_enc, g_enc_stride, nullptr, 0, nullptr, L.nwg, L.m, counts, total, rec_idx, rec_val, level_mask, level_max);
-    } else {
-        if (g_jac) hash_bin_kernel<true, false><<<L.nwg, THREADS, 0, s>>>(n, x, c, b, g_enc, g_enc_stride, g_jac, g_jac_stride, q, L.nwg, counts, rec_idx, rec_val, level_mask, level_max);
-        else hash_bin_kernel<false, false><<<L.nwg, THREADS, 0, s>>>(n, x, c, b, g_enc, g_enc_stride, nullptr, 0, nullptr, L.nwg, counts, rec_idx, rec_val, level_mask, level_max);
-    }
+    if (g_jac) hash_bin_unit_kernel<true, false><<<ugrid, THREADS, lds_count, s>>>(n, x, c, b, g_enc, g_enc_stride, g_jac, g_jac_stride, q, L.nwg, L.m, counts, total, rec_idx, rec_val, level_mask, level_max);
+    else hash_bin_unit_kernel<false, false><<<ugrid, THREADS, lds_count, s>>>(n, x, c, b, g_enc, g_enc_stride, nullptr, 0, nullptr, L.nwg, L.m, counts, total, rec_idx, rec_val, level_mask, level_max);
     int r = ia_exclusive_scan_i32(counts, counts, total, L.m, tmp, stream);
     if (r != IA_OK) return r;
     static bool attr_fill = false;
-    if (staged && !attr_fill) {
+    if (!attr_fill) {
         (void)hipFuncSetAttribute((const void*)hash_bin_unit_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fill);
         (void)hipFuncSetAttribute((const void*)hash_bin_unit_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fill);
         (void)hipGetLastError();
         attr_fill = true;
     }
-    if (staged) {
-        if (g_jac) hash_bin_unit_kernel<true, true><<<ugrid, THREADS, lds_fill, s>>>(n, x, c, b, g_enc, g_enc_stride, g_jac, g_jac_stride, q, L.nwg, L.m, counts, total, rec_idx, rec_val, level_mask, level_max);
-        else hash_bin_unit_kernel<false, true><<<ugrid, THREADS, lds_fill, s>>>(n, x, c, b, g_enc, g_enc_stride, nullptr, 0, nullptr, L.nwg, L.m, counts, total, rec_idx, rec_val, level_mask, level_max);
-    } else {
-        if (g_jac) hash_bin_kernel<true, true><<<L.nwg, THREADS, 0, s>>>(n, x, c, b, g_enc, g_enc_stride, g_jac, g_jac_stride, q, L.nwg, counts, rec_idx, rec_val, level_mask, level_max);
-        else hash_bin_kernel<false, true><<<L.nwg, THREADS, 0, s>>>(n, x, c, b, g_enc, g_enc_stride, nullptr, 0, nullptr, L.nwg, counts, rec_idx, rec_val, level_mask, level_max);
-    }
+    if (g_jac) hash_bin_unit_kernel<true, true><<<ugrid, THREADS, lds_fill, s>>>(n, x, c, b, g_enc, g_enc_stride, g_jac, g_jac_stride, q, L.nwg, L.m, counts, total, rec_idx, rec_val, level_mask, level_max);
+    else hash_bin_unit_kernel<false, true><<<ugrid, THREADS, lds_fill, s>>>(n, x, c, b, g_enc, g_enc_stride, nullptr, 0, nullptr, L.nwg, L.m, counts, total, rec_idx, rec_val, level_mask, level_max);
     static bool attr = false;
     constexpr size_t red_lds = (size_t)SLICE * 2 * sizeof(unsigned long long);      // 128 KB
     if (!attr) {

@@ -638,7 +638,7 @@ static int launch_fine(int64_t n_rays, int64_t n_in, int n, const int32_t* packe
 {
     if (n_rays == 0) return IA_OK;
     const int grid = ia::cdiv(n_rays, THREADS);
-    if (n + 1 <= IA_RS_SMALL && getenv("IA_RESAMPLE_TABLES") == nullptr) {
+    if (n + 1 <= IA_RS_SMALL) {
         const int bins = n + 1;
         const float du = (float)((1.0f - 1.0 / bins) / n);
         const float u0 = (float)(1.0 / (2 * bins));

@@ -1618,12 +1618,10 @@ IA_EXPORT int ia_fuse_broyden(int B, int64_t N, int I, const float* xd_tgt, cons
     bool persistent = total >= (int64_t)32 << 20;
     if (const char* e = getenv("IA_BROYDEN_SCHEDULE")) persistent = (e[0] == 'p');     // test hook: "persistent" / "simple"
     if (persistent) {
-        int br_chunk = BR_CHUNK;
-        if (const char* e = getenv("IA_BR_CHUNK")) br_chunk = atoi(e);                   // tuning hook
+        const int br_chunk = BR_CHUNK;
         const int64_t n_waves = (total + br_chunk - 1) / br_chunk;
         const int grid = ia::cdiv(n_waves * 64, THREADS);
-        const char* v = getenv("IA_BROYDEN_V2");
-        if (B == 1 && layout == IA_LAYOUT_NDHWC && I >= 2 && I <= 16 && br_chunk < (1 << 24) && !(v && v[0] == '0')) {
+        if (B == 1 && layout == IA_LAYOUT_NDHWC && I >= 2 && I <= 16) {
             // umulhi(t, ceil(2^32 / I)) == t / I while t * (magic * I - 2^32) < 2^32, i.e. for every t < 2^28
             const uint32_t magic = (uint32_t)((((uint64_t)1 << 32) + (uint64_t)I - 1) / (uint64_t)I);
             broyden_persistent2_kernel<<<grid, THREADS, 0, s>>>(total, I, magic, xd_tgt, voxel_J, D, H, W, tfs, bone_ids, offset, scale,
@@ -1662,70 +1660,36 @@ static int launch_spec(bool pack, int64_t N, int I, const float* xd_tgt, const f
     IA_REQUIRE(eps >= 0.0f, "early-filter search: eps must be >= 0");
     IA_REQUIRE((int64_t)D * H * W < ((int64_t)1 << 26), "voxel grid too large for 32-bit byte offsets (48 B per voxel)");
     IA_REQUIRE(N < ((int64_t)1 << 31), "early-filter search: N must stay below 2^31");
-    // chunk = 2^log2c consecutive points of the sorted order, shared by the four waves of a workgroup.  Same-box A/B on the 16.4 M headline
-    // march points (tools/search_ab.py, search + rows ms): one chunk per workgroup with 2^7 / 2^8 / 2^9 / 2^10 points 10.68 / 8.81 / 9.05 /
-    // 9.73 (round 3's 768: 9.41) -- ONE POINT PER LANE is best: what a short chunk loses to its slowest point it wins back through the
-    // narrower window of the sorted order the resident workgroups cover (1280 x 256 points).  PERSISTENT workgroups that walk the chunks
-    // b, b + G, ... as one stream (no drain at all; IA_BR_SPEC_PERSIST=1) lose badly, 13.6 - 14.7 ms: with a static stride the
-    // workgroups drift apart by whole rounds and the window grows to several G x 2^log2c points -- the hardware's in-order dispatch of
-    // one-chunk workgroups IS the dynamic queue that keeps the window tight.  Chunks of MORE points than lanes (the lanes that finish first
-    // take the extra ones while the chunk's slow points are still running) lose as well: 288 / 320 / 384 points per 256 lanes 10.11 / 9.94 /
-    // 9.70 ms against 8.90 (same box, search + rows): a second point started late in the workgroup's life extends it by a whole search.
-    int log2c = 8;
-    if (const char* e = getenv("IA_BR_SPEC_LOG2C")) { const int v = atoi(e); if (v >= 6 && v <= 14) log2c = v; }
-    const int64_t n_chunks = (N + ((int64_t)1 << log2c) - 1) >> log2c;
-    int grid = (int)n_chunks;
-    if (const char* e = getenv("IA_BR_SPEC_PERSIST")) {
-        if (atoi(e) == 1) {
-            static int resident = 0;
-            if (resident == 0) {
-                int dev = 0, cus = 256, per_cu = 5;
-                (void)hipGetDevice(&dev);
-                (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, broyden_spec_kernel<false, true>, THREADS, 0);
-                (void)hipGetLastError();
-                resident = (cus > 0 ? cus : 256) * (per_cu > 0 ? per_cu : 5);
-            }
-            grid = (int)(n_chunks < resident ? n_chunks : resident);
-        }
-    }
-    IA_REQUIRE(n_chunks < ((int64_t)1 << 31) && (N >> log2c) / grid < ((int64_t)1 << (30 - log2c)), "early-filter search: stream positions must fit 31 bits");
-    const int pts = log2c;
-    int wg_env = THREADS;
-    if (const char* e = getenv("IA_BR_SPEC_WG")) { const int v = atoi(e); if (v == 64 || v == 128) wg_env = v; }
+    // chunk = 2^8 consecutive points of the sorted order, shared by the four waves of a workgroup, one chunk per workgroup.  Same-box A/B on the
+    // 16.4 M headline march points (tools/search_ab.py, search + rows ms): chunks of 2^7 / 2^8 / 2^9 / 2^10 points took 10.68 / 8.81 / 9.05 /
+    // 9.73 (round 3's 768: 9.41) -- ONE POINT PER LANE was best: what a short chunk loses to its slowest point it wins back through the
+    // narrower window of the sorted order the resident workgroups cover (1280 x 256 points).  PERSISTENT workgroups that walked the chunks
+    // b, b + G, ... as one stream (no drain at all) lost badly, 13.6 - 14.7 ms: with a static stride the workgroups drifted apart by whole
+    // rounds and the window grew to several G x 2^8 points -- the hardware's in-order dispatch of one-chunk workgroups IS the dynamic
+    // queue that keeps the window tight.  Chunks of MORE points than lanes (the lanes that finish first took the extra ones while the
+    // chunk's slow points were still running) lost as well: 288 / 320 / 384 points per 256 lanes 10.11 / 9.94 / 9.70 ms against 8.90 (same
+    // box, search + rows): a second point started late in the workgroup's life extended it by a whole search.  Workgroups of 64 / 128
+    // lanes and 8 KB of unused dynamic LDS (four workgroups per CU instead of five, to leave room for another stream's kernel) were
+    // measured without effect.  All of these variants are retired: tools/experiments/retired_ab_variants.patch.
+    const int pts = 8;
+    const int grid = (int)((N + ((int64_t)1 << pts) - 1) >> pts);
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* c = reinterpret_cast<unsigned long long*>(counters);
     int slots = SPEC_ROOTS;                                              // test hook: fewer recorded roots / row slots => more points take the exact redo
     if (const char* e = getenv("IA_SPEC_TEST_SLOTS")) { const int v = atoi(e); if (v >= 1 && v <= SPEC_ROOTS) slots = v; }
-    // IA_BR_SPEC_PAD_LDS = bytes of (unused) dynamic LDS added to the launch: 31.5 KB of static LDS let five workgroups share a CU's 160 KB;
-    // 8 KB more make it four (96 VGPRs x 4 waves per SIMD: 128 VGPRs per SIMD stay free for ONE wave of another stream's kernel that
-    // needs no LDS -- the hash gather, 104 VGPRs).  Used with the search token of deformer.py (one search on the device at a time).
-    static int pad_lds = -1;
-    if (pad_lds < 0) { const char* e = getenv("IA_BR_SPEC_PAD_LDS"); const int v = e ? atoi(e) : 0; pad_lds = (v > 0 && v <= 32768) ? v : 0; }
     // IA_BR_SPEC_SCALAR = 1 (default): the leader cell of each wave's fetch is served through the scalar memory path (grid_sample_J's
     // SCELLS); 0: every lane through the vector path.  Read at every launch: a same-process A/B and the tests switch it without a rebuild.
     int scells = 1;
     if (const char* e = getenv("IA_BR_SPEC_SCALAR")) scells = atoi(e) == 0 ? 0 : 1;
 #define IA_SPEC_LAUNCH_S(COUNT, PACK, SC)                                                                                                    \
-    broyden_spec_kernel<COUNT, PACK, THREADS, SC><<<grid, THREADS, pad_lds, s>>>(N, I, xd_tgt, voxel_J_cl, D, H, W, tfs, bone_ids, offset, scale, \
-                                                                                 cvg_threshold, dvg_threshold, eps, x, J_inv, is_valid, fwd_J, pts, c, \
-                                                                                 cnt, meta, flag, slots, order, cell_tight)
+    broyden_spec_kernel<COUNT, PACK, THREADS, SC><<<grid, THREADS, 0, s>>>(N, I, xd_tgt, voxel_J_cl, D, H, W, tfs, bone_ids, offset, scale,   \
+                                                                           cvg_threshold, dvg_threshold, eps, x, J_inv, is_valid, fwd_J, pts, c, \
+                                                                           cnt, meta, flag, slots, order, cell_tight)
 #define IA_SPEC_LAUNCH(COUNT, PACK)                                                                                                    \
     do {                                                                                                                               \
         if (scells == 0) IA_SPEC_LAUNCH_S(COUNT, PACK, 0);                                                                             \
         else IA_SPEC_LAUNCH_S(COUNT, PACK, 1);                                                                                         \
     } while (0)
-    if (pack && !counters && wg_env != THREADS) {
-        // A / B: smaller workgroups (one point per lane each): IA_BR_SPEC_WG = 64 | 128, chunk = the workgroup's lanes
-        if (wg_env == 64)
-            broyden_spec_kernel<false, true, 64><<<(int)((N + 63) / 64), 64, 0, s>>>(N, I, xd_tgt, voxel_J_cl, D, H, W, tfs, bone_ids, offset, scale, cvg_threshold,
-                                                                                     dvg_threshold, eps, x, J_inv, is_valid, fwd_J, 6, c, cnt, meta, flag, slots, order, cell_tight);
-        else
-            broyden_spec_kernel<false, true, 128><<<(int)((N + 127) / 128), 128, 0, s>>>(N, I, xd_tgt, voxel_J_cl, D, H, W, tfs, bone_ids, offset, scale,
-                                                                                         cvg_threshold, dvg_threshold, eps, x, J_inv, is_valid, fwd_J, 7, c, cnt, meta, flag,
-                                                                                         slots, order, cell_tight);
-        return ia::check_launch(what);
-    }
     if (pack) { if (counters) IA_SPEC_LAUNCH(true, true); else IA_SPEC_LAUNCH(false, true); }
     else { if (counters) IA_SPEC_LAUNCH(true, false); else IA_SPEC_LAUNCH(false, false); }
 #undef IA_SPEC_LAUNCH

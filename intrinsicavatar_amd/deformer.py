@@ -29,13 +29,13 @@ class SNARFDeformer:
     # the filter off; a root in a voxel cell where the TRUE Jacobian of the skinning map is not tight everywhere (cell_tight: per pose,
     # fast_snarf.cell_tightness) retires nothing -- next to a fold of the map Broyden's estimate is blind.  The candidate set equals
     # search-to-the-end + K9 on every point measured (0 of 145 M march points on the eight reference poses,
-    # profiles/r04_spec_search_probe_poses.jsonl; without the cell table 3e-7 of them differed), candidates bit-identical.  IA_SPEC_CELL_TAU=0
-    # switches the table off (A / B).  On for EVERY batch size: what a point gets must not
+    # profiles/r04_spec_search_probe_poses.jsonl; without the cell table 3e-7 of them differed), candidates bit-identical.
+    # On for EVERY batch size: what a point gets must not
     # depend on how many other points share its launch (ray-batch sharding invariance, multi-GPU = single GPU).
     # IA_BROYDEN_SPEC_EPS=0 (or deformer.spec_eps = 0) = the reference's search-to-the-end everywhere; the kernel-level parity tests
     # (K8 / K9 golden vectors) call those entry points directly.
     SPEC_EPS = float(os.environ.get("IA_BROYDEN_SPEC_EPS", "1e-3"))
-    SPEC_MIN_POINTS = int(os.environ.get("IA_BROYDEN_SPEC_MIN_POINTS", "1"))
+    SPEC_MIN_POINTS = 1
 
     def __init__(self, lbs_voxel_final: Tensor, offset_kernel: Tensor, scale_kernel: Tensor, bbox: Tensor):
         self.lbs_voxel_final = lbs_voxel_final.contiguous().float()          # [1,24,D,H,W]
@@ -114,9 +114,8 @@ class SNARFDeformer:
         # to the first size read-back of a search on this pose (_check_voxels) -- no host sync of its own
         self._voxels_finite = torch.isfinite(self.voxel_J_cl).all()
         # veto table of the early filter: cells where the true Jacobian of the skinning map is tight (one small kernel per pose)
-        tau = float(os.environ.get("IA_SPEC_CELL_TAU", str(fast_snarf.CELL_TAU)))
-        self.cell_tight = (fast_snarf.cell_tightness(fast_snarf.ChannelLastVoxelJ(self.voxel_J_cl), self.offset_kernel, self.scale_kernel, tau)
-                           if (tau > 0 and B == 1) else None)
+        self.cell_tight = (fast_snarf.cell_tightness(fast_snarf.ChannelLastVoxelJ(self.voxel_J_cl), self.offset_kernel, self.scale_kernel)
+                           if B == 1 else None)
 
     def _check_voxels(self):
         f = self._voxels_finite
@@ -239,11 +238,7 @@ class SNARFDeformer:
         L.lib().ia_deform_pack_tiles(P, I, x, src, start, cand_x, cand_src, tmp)
         return cand_x, cand_src, cnt, start, Q
 
-    SPEC_ROWS = os.environ.get("IA_BROYDEN_SPEC_ROWS", "1") == "1"
-    SEARCH_TOKEN = os.environ.get("IA_SEARCH_TOKEN", "0") == "1"
-    SEARCH_TOKEN_MIN_POINTS = int(os.environ.get("IA_SEARCH_TOKEN_MIN_POINTS", str(1 << 22)))
-    _search_lock = __import__("threading").Lock()
-    _search_event = None
+    SPEC_ROWS = True
 
     @torch.no_grad()
     def _candidates(self, pts: Tensor, with_src: bool, want_fwd: bool = False, want_jinv: bool = False, order: Optional[Tensor] = None,
@@ -276,32 +271,13 @@ class SNARFDeformer:
         ovf_scratch = L.work_area(L.lib().ia_spec_rows_overflow_bytes(P), dev, "spec_rows")
         ovf_cap = self._tls.ovf_cap = int(L.lib().ia_spec_rows_overflow_capacity(P))
         tot = torch.empty(2, dtype=torch.int32, device=dev)
-        # IA_SEARCH_TOKEN=1 (experiment, measured without effect -- DESIGN 4.5): one search on the DEVICE at a time; this stream's search
-        # starts when the previous search of any stream has finished, so that a search shares the device with another stream's gather /
-        # head kernels instead of with another search
-        token = self.SEARCH_TOKEN and P >= self.SEARCH_TOKEN_MIN_POINTS
-        if token:
-            self._search_lock.acquire()
-        try:
-            if token and self._search_event is not None:
-                torch.cuda.current_stream(dev).wait_event(self._search_event)
-            fast_snarf.fuse_broyden_spec_rows(x_rows, pts.reshape(1, P, 3), fast_snarf.ChannelLastVoxelJ(self.voxel_J_cl), self.tfs, self.init_bones,
-                                              Jinv, cnt, meta, start, ovf_head, ovf_scratch, tot, self.offset_kernel, self.scale_kernel,
-                                              1e-5, 1e-1, self.spec_eps, fwd_J=fwd, counters=self.spec_counters, order=order,
-                                              cell_tight=self.cell_tight)
-            if token:
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
-                type(self)._search_event = ev
-        finally:
-            if token:
-                self._search_lock.release()
+        fast_snarf.fuse_broyden_spec_rows(x_rows, pts.reshape(1, P, 3), fast_snarf.ChannelLastVoxelJ(self.voxel_J_cl), self.tfs, self.init_bones,
+                                          Jinv, cnt, meta, start, ovf_head, ovf_scratch, tot, self.offset_kernel, self.scale_kernel,
+                                          1e-5, 1e-1, self.spec_eps, fwd_J=fwd, counters=self.spec_counters, order=order,
+                                          cell_tight=self.cell_tight)
         Q, n_over = tot.tolist()                                     # the one read-back of the call
         self._tls.n_over = n_over                                    # points the kernel searched again with the filter off
         self._check_voxels()
-        if os.environ.get("IA_DEBUG_FLAGGED"):
-            import sys
-            print(f"[spec rows] P={P} Q={Q} redone={n_over} ({n_over / max(P, 1):.2e}) cap={ovf_cap}", file=sys.stderr)
         if n_over > ovf_cap:
             # more points to redo than the flagged list holds (never seen): this batch goes through is_valid + K9 instead
             del x_rows, cnt, meta, start, Jinv, fwd
@@ -330,7 +306,7 @@ class SNARFDeformer:
         return res + (None, None) if split else res
 
     # the SDF-only queries gather their candidates in the split layout (first candidates, then the rest: -6 % in the hash gather)
-    SPLIT_CANDIDATES = os.environ.get("IA_SPLIT_CANDIDATES", "1") == "1"
+    SPLIT_CANDIDATES = True
     SPEC_CANARY = int(os.environ.get("IA_SPEC_CANARY", "0"))
 
     @torch.no_grad()

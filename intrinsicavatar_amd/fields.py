@@ -65,9 +65,9 @@ def hashgrid_backward(x01: Tensor, g_enc: Optional[Tensor], grad_params: Tensor,
                       g_jac: Optional[Tensor] = None, q: Optional[Tensor] = None, method: Optional[str] = None,
                       level_mask: int = 0xFFFFFFFF):
     """accumulate d L / d table into grad_params (see include/ia_amd.h ia_hashgrid_bwd / ia_hashgrid_bwd_binned).
-    method: None (by batch size; env IA_HASH_BWD overrides) | 'atomic' | 'binned'."""
+    method: None (by batch size) | 'atomic' | 'binned'."""
     n = x01.shape[0]
-    method = method or os.environ.get("IA_HASH_BWD") or ("binned" if n >= HASH_BWD_BINNED_MIN else "atomic")
+    method = method or ("binned" if n >= HASH_BWD_BINNED_MIN else "atomic")
     cargs = (cfg["n_levels"], cfg["n_features_per_level"], cfg["log2_hashmap_size"], cfg["base_resolution"], cfg["per_level_scale"])
     if method == "atomic":
         L.lib().ia_hashgrid_bwd(n, x01, *cargs, g_enc, g_enc.stride(0) if g_enc is not None else 0, g_jac,
@@ -330,7 +330,7 @@ class VolumeSDF(nn.Module):
         output layer is summed in another order (last-bit differences).  normalized: `points` are already the hash grid's
         coordinates (points - center) / scale + 0.5."""
         n = points.shape[0]
-        if n == 0 or os.environ.get("IA_SDF_ONLY_FUSED", "1") != "1":
+        if n == 0:
             if normalized:
                 points = (points - 0.5) * self.scale + self.center
             return self.forward(points, with_grad=False, with_feature=False).contiguous()

@@ -9,7 +9,6 @@ lib/torch_pbr is an empty submodule in the reference tree; semantics are those o
 (standard Lambert + GGX multi-lobe BRDF, luminance x sin(theta) importance-sampled equirect light).
 Random numbers are explicit inputs."""
 import math
-import os
 from typing import Dict, Optional
 
 
@@ -453,8 +452,7 @@ class VolumeInteraction:
     where each ray's / each source interval's foreground re-samples sit in the ray-major foreground list [F].
     Everything sample_volume_interaction (models/pbr/utils.py:70-229) derives with nonzero / gathers / scatters comes
     out of scans and streaming kernels; the only host read-back is (R, F) -- K1's own total and the foreground count, together."""
-    K1_CAPACITY = os.environ.get("IA_K1_CAPACITY", "1") == "1"
-    K1_CAPACITY_MAX_SLOTS = int(os.environ.get("IA_K1_CAPACITY_MAX_SLOTS", str(1 << 24)))
+    K1_CAPACITY_MAX_SLOTS = 1 << 24
 
     @torch.no_grad()
     def __init__(self, ray_indices: Tensor, t_starts: Tensor, t_ends: Tensor, n_rays: int, spp: int, weights: Tensor, sdfs: Tensor):
@@ -462,11 +460,11 @@ class VolumeInteraction:
         self.n_rays, self.spp = n_rays, spp
         self.packed_info = lib_nerfacc.pack_info(ray_indices, n_rays)
         # K1's own size (cdf.cu:183) is not read back on its own: its per-resample outputs are written into n_rays x spp slots, the total R
-        # stays on the device and comes back TOGETHER with the foreground count F below (IA_K1_CAPACITY=0: two read-backs, the A/B hook)
+        # stays on the device and comes back TOGETHER with the foreground count F below
         totals = torch.empty(2, dtype=torch.int32, device=dev)          # [R, F], both written by scans
         # (ray BATCHES only: for a whole 540 x 540 frame at spp 1024 the 299 M slots -- a quarter of them used -- cost 3 GiB and ~1 ms per
         #  step, measured, against one read-back of 21: profiles/r06_k1_capacity_ab.jsonl)
-        capacity = self.K1_CAPACITY and n_rays * spp <= self.K1_CAPACITY_MAX_SLOTS
+        capacity = n_rays * spp <= self.K1_CAPACITY_MAX_SLOTS
         if capacity:
             (self.resampled_packed_info, self.ts, self.offsets, self.sampled_idx, self.fg_counts, self.bg_counts,
              self.surface_idx) = lib_nerfacc.ray_resampling_capacity(self.packed_info, t_starts[:, None], t_ends[:, None], weights.detach(),

@@ -117,9 +117,8 @@ class RenderStep:
     # points per deformer search: P * 13 (point, init) items must stay below 2^31 (165.2 M points) and x / valid take 169 B per
     # point (25 GB at 150 M); the headline step's 16 Mi-ray secondary chunks average 145 M sample points
     MAX_SEARCH_POINTS = int(os.environ.get("IA_MAX_SEARCH_POINTS", str(150_000_000)))
-    K2_MERGED_READBACK = os.environ.get("IA_K2_MERGED_READBACK", "1") == "1"
 
-    SORT_DROP_BITS = int(os.environ.get("IA_SORT_DROP_BITS", "0"))     # low Morton bits left unsorted (0, 3 or 6)
+    SORT_DROP_BITS = 0     # low Morton bits left unsorted (0, 3 or 6)
 
     def _sort_grid_params(self):
         """(origin, 1 / cell) of the Morton grid of _spatial_order, cached per occupancy box (ONE attribute assignment: several host threads
@@ -131,7 +130,7 @@ class RenderStep:
             # a 2.5 m box.  Measured on the headline step: 1 cm cells 970 ms, 5 mm 948 ms, 2.5 mm 946 ms, 4 cm 1019 ms
             box = self.aabbs[0].tolist()
             ext = max(box[3] - box[0], box[4] - box[1], box[5] - box[2]) + 0.04
-            c = (gkey, [box[0] - 0.02, box[1] - 0.02, box[2] - 0.02], float(os.environ.get("IA_SORT_INV_CELL", 1023.0 / ext)))
+            c = (gkey, [box[0] - 0.02, box[1] - 0.02, box[2] - 0.02], 1023.0 / ext)
             self._sort_grid_cache = c
         return c[1], c[2]
 
@@ -203,14 +202,10 @@ class RenderStep:
                     sdf_curr = self._sdf_at(pts)
                     alphas = laplace_alpha(smp.to_edges(sdf_curr, 1e10), smp.to_edges(smp.t_ends - smp.t_starts, 0.0), beta)
                 weights, _ = nerfacc.render_weight_from_alpha(alphas, packed_info=intervals.packed_info)
-                # K2 + the selection of its reached edges (intrinsic_avatar.py:1211-1226) as count -> scan -> fill kernels
-                if self.K2_MERGED_READBACK:
-                    rvals, ril, rir, ray_idx, pinfo, smp_next = lib_nerfacc.ray_resampling_merge_compact_samples(
-                        intervals.packed_info, vals, intervals.is_left, intervals.is_right, weights, 16)
-                else:           # IA_K2_MERGED_READBACK=0 (A/B hook): K2's edge count and the sample count in two read-backs
-                    rvals, ril, rir, ray_idx, pinfo = lib_nerfacc.ray_resampling_merge_compact(
-                        intervals.packed_info, vals, intervals.is_left, intervals.is_right, weights, 16)
-                    smp_next = lib_nerfacc.interval_samples(pinfo, rvals, ril, ray_idx)
+                # K2 + the selection of its reached edges (intrinsic_avatar.py:1211-1226) as count -> scan -> fill kernels; K2's edge
+                # count and the sample count come back in one read-back
+                rvals, ril, rir, ray_idx, pinfo, smp_next = lib_nerfacc.ray_resampling_merge_compact_samples(
+                    intervals.packed_info, vals, intervals.is_left, intervals.is_right, weights, 16)
                 intervals = RayIntervals(vals=rvals, is_left=ril, is_right=rir, ray_indices=ray_idx, packed_info=pinfo)
         # -- 4.
         smp = smp_next if smp_next is not None else \
@@ -399,7 +394,7 @@ class RenderStep:
     import threading as _threading
     _march_hooks = _threading.local()          # per host thread: .enter (callable) / .streams (override of SECONDARY_STREAMS)
     SECONDARY_STREAMS = int(os.environ.get("IA_SECONDARY_STREAMS", "2"))
-    STREAM_FALLBACK_COOLDOWN = int(os.environ.get("IA_STREAM_FALLBACK_COOLDOWN", "64"))
+    STREAM_FALLBACK_COOLDOWN = 64
     # bytes of device memory a marched ray of a chunk keeps live at the peak of its chunk on the headline scene (9 samples per ray on
     # average x (search outputs + sorted copies + level-major hash features)): 142 GiB live for 2 x 10.5 Mi rays = ~7 KB per ray
     SECONDARY_BYTES_PER_RAY = int(os.environ.get("IA_SECONDARY_BYTES_PER_RAY", "7168"))

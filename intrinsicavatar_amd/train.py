@@ -5,19 +5,18 @@ The reference trains through `rgb_normal_alpha_fn` + `rendering_with_normals_sdf
 including the double backward through the analytic normal (models/rf/geometry.py:165-172).  Here
 each stage is a torch.autograd.Function whose forward AND backward are HIP kernels behind the C ABI:
 
-    _SDFField      hash grid + SDF MLP -> (feature[13], d sdf/d x)      ia_hashgrid_fwd/bwd, ia_mlp_fwd, ia_sdf_mlp_bwd
+    _SDFField      hash grid + SDF MLP -> (feature[13], d sdf/d x)      ia_hashgrid_fwd/bwd, ia_mlp_fwd, ia_sdf_mlp_bwd_fused
     _ShadePrep     normals / reflected direction                         ia_shade_prep(_bwd)
     _Alpha         Laplace density -> alpha                              ia_laplace_alpha(_bwd)
-    _Radiance      hash grid #2 + SH + radiance MLP                      ia_hashgrid_fwd/bwd, ia_sh4_fwd/bwd, ia_mlp_fwd/bwd
+    _Radiance      hash grid #2 + SH + radiance MLP                      ia_hashgrid_fwd/bwd, ia_sh4_fwd/bwd, ia_mlp_fwd, ia_mlp_bwd_fused
     nerfacc._WeightFromAlpha / _Accumulate                               ia_render_weight_from_alpha(_bwd), ia_accumulate_*(_bwd)
 
 Sample positions, the candidate search and the winner selection are not differentiated, exactly as in the
-reference (resampling under no_grad; torch.gather passes gradients to the winning candidate only).  The tiny
-weight-gradient reductions dW = G^T A ([64 x n] x [n x <=68]) use the split-K MFMA kernel ia_wgrad (rocBLAS maps this
-shape to a single output tile walking K = millions of points).
+reference (resampling under no_grad; torch.gather passes gradients to the winning candidate only).  The MLP backward
+kernels (csrc/mlp_train.hip) reduce the weight gradients themselves; wgrad() is the stand-alone split-K MFMA reduction
+dW = G^T A ([64 x n] x [n x <=68]; rocBLAS maps this shape to a single output tile walking K = millions of points).
 """
 import math
-import os
 from typing import Dict, Optional
 
 import torch
@@ -26,10 +25,6 @@ from torch.autograd import Function
 
 from . import _lib as L
 from . import fields, lib_nerfacc, nerfacc, render
-
-
-# fused data + weight backward (csrc/mlp_train.hip); False = operand pairs through HBM + ia_wgrad (csrc/mlp_bwd.hip)
-FUSED_WGRAD = os.environ.get("IA_FUSED_WGRAD", "1") != "0"
 
 
 def wgrad(G: Tensor, M: int, A: Tensor, N: int, want_bias: bool = True):
@@ -75,29 +70,18 @@ class _SDFField(Function):
         gE, gG = torch.empty((n, 32), device=dev), torch.empty((n, 32), device=dev)
         ns, ptrs, strides, widths, muls, adds = _segs([(enc, 32, 1.0, 0.0), (xp, 3, 2.0, -1.0)])
         g_table = L.zeros_like(table)
-        if FUSED_WGRAD:
-            dW1k, db1, dW2, db2 = zeros_like_shapes([(64, 35), (64,), (13, 64), (13,)], dev)
-            want_x = ctx.needs_input_grad[0]
-            g_xyz = torch.empty((n, 3), device=dev) if want_x else None
-            L.lib().ia_sdf_mlp_bwd_fused(n, ns, ptrs, strides, widths, muls, adds, W1k, b1, W2, b2, jac, g_y, q, gE, gG, dW1k, db1, dW2, db2, g_xyz)
-            fields.hashgrid_backward(xp, gE, g_table, g_jac=gG, q=q, level_mask=ctx.level_bits)
-            g_x = None
-            if want_x:
-                # first-order d L / d x (pose gradients, SNARF's implicit differentiation): J_enc^T gE + 2 g_xyz, / scale.
-                # The dependence of the analytic normal on x (a Hessian term; tiny-cuda-nn returns zero for it too) is dropped.
-                g_x = (_jac_contract_T(jac, gE) + 2.0 * g_xyz) / scale
-            return g_x, g_table, dW1k, db1, dW2, db2, None, None, None, None
-        if ctx.needs_input_grad[0]:
-            raise NotImplementedError("pose gradients (d L / d x_cano) are only produced by the fused backward (FUSED_WGRAD)")
-        Hh, U = torch.empty((n, 36), device=dev), torch.empty((n, 36), device=dev)
-        DZ, GZ, A, DGS = (torch.empty((n, 64), device=dev) for _ in range(4))
-        L.lib().ia_sdf_mlp_bwd(n, ns, ptrs, strides, widths, muls, adds, W1k, b1, W2, b2, jac, g_y, q, gE, gG, Hh, U, DZ, GZ, A, DGS)
+        # fused data + weight backward (csrc/mlp_train.hip)
+        dW1k, db1, dW2, db2 = zeros_like_shapes([(64, 35), (64,), (13, 64), (13,)], dev)
+        want_x = ctx.needs_input_grad[0]
+        g_xyz = torch.empty((n, 3), device=dev) if want_x else None
+        L.lib().ia_sdf_mlp_bwd_fused(n, ns, ptrs, strides, widths, muls, adds, W1k, b1, W2, b2, jac, g_y, q, gE, gG, dW1k, db1, dW2, db2, g_xyz)
         fields.hashgrid_backward(xp, gE, g_table, g_jac=gG, q=q, level_mask=ctx.level_bits)
-        dW1k, db1 = wgrad(DZ, 64, Hh, 35)
-        dW1k = dW1k + wgrad(GZ, 64, U, 35, want_bias=False)[0]
-        dW2, db2 = wgrad(g_y, 13, A, 64)
-        dW2[0] += wgrad(DGS, 64, DGS, 1)[1]          # column sums of DGS
-        return None, g_table, dW1k, db1, dW2, db2, None, None, None, None
+        g_x = None
+        if want_x:
+            # first-order d L / d x (pose gradients, SNARF's implicit differentiation): J_enc^T gE + 2 g_xyz, / scale.
+            # The dependence of the analytic normal on x (a Hessian term; tiny-cuda-nn returns zero for it too) is dropped.
+            g_x = (_jac_contract_T(jac, gE) + 2.0 * g_xyz) / scale
+        return g_x, g_table, dW1k, db1, dW2, db2, None, None, None, None
 
 
 class _ShadePrep(Function):
@@ -250,18 +234,8 @@ class _Radiance(Function):
         g_x = torch.empty((n, 68), device=dev)
         segs = [(enc, 32, 1.0, 0.0), (xp, 3, 2.0, -1.0), (feat, 13, 1.0, 0.0), (sh, 16, 1.0, 0.0), (normal_world, 3, 1.0, 0.0)]
         ns, ptrs, strides, widths, muls, adds = _segs(segs)
-        if FUSED_WGRAD:
-            dW1, db1, dW2, db2, dW3, db3 = zeros_like_shapes([(64, 67), (64,), (64, 64), (64,), (3, 64), (3,)], dev)
-            L.lib().ia_mlp_bwd_fused(1, n, ns, ptrs, strides, widths, muls, adds, W1k, b1, W2, b2, W3, b3, g_rgb, g_x, 68, dW1, db1, dW2, db2, dW3,
-                                     db3)
-        else:
-            X = torch.empty((n, 68), device=dev)
-            A1, A2, G1, G2 = (torch.empty((n, 64), device=dev) for _ in range(4))
-            G3 = torch.empty((n, 16), device=dev)
-            L.lib().ia_mlp_bwd(1, n, ns, ptrs, strides, widths, muls, adds, W1k, b1, W2, b2, W3, b3, g_rgb, g_x, 68, X, A1, A2, G1, G2, G3)
-            dW1, db1 = wgrad(G1, 64, X, 67)
-            dW2, db2 = wgrad(G2, 64, A1, 64)
-            dW3, db3 = wgrad(G3, 3, A2, 64)
+        dW1, db1, dW2, db2, dW3, db3 = zeros_like_shapes([(64, 67), (64,), (64, 64), (64,), (3, 64), (3,)], dev)
+        L.lib().ia_mlp_bwd_fused(1, n, ns, ptrs, strides, widths, muls, adds, W1k, b1, W2, b2, W3, b3, g_rgb, g_x, 68, dW1, db1, dW2, db2, dW3, db3)
         g_table = L.zeros_like(table)
         fields.hashgrid_backward(xp, g_x, g_table, level_mask=ctx.level_bits)      # columns 0..31, row stride 68
         g_feat = g_x[:, 35:48]

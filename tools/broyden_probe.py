@@ -37,8 +37,8 @@ def run():
 res = dict(points=P, samples_per_ray=P / n_sec)
 _, _, D, H, W = dfm.lbs_voxel_final.shape
 ref_out = None
-for sched, v2 in (("persistent", "0"), ("persistent", "1"), ("simple", "1")):
-    os.environ["IA_BROYDEN_SCHEDULE"], os.environ["IA_BROYDEN_V2"] = sched, v2
+for sched in ("persistent", "simple"):
+    os.environ["IA_BROYDEN_SCHEDULE"] = sched
     x.fill_(0); valid.fill_(False)
     run(); torch.cuda.synchronize()
     cur = (valid.clone(), torch.where(valid[..., None], x, torch.zeros_like(x)))
@@ -50,8 +50,7 @@ for sched, v2 in (("persistent", "0"), ("persistent", "1"), ("simple", "1")):
     e0.record()
     for _ in range(3): run()
     e1.record(); torch.cuda.synchronize()
-    res[sched + ("_v2" if (v2 == "1" and sched == "persistent") else "") + "_ms"] = e0.elapsed_time(e1) / 3
-os.environ["IA_BROYDEN_V2"] = os.environ.get("IA_PROBE_V2", "1")
+    res[sched + "_ms"] = e0.elapsed_time(e1) / 3
 def stats_for(points):
     c = torch.zeros(17, dtype=torch.int64, device=dev)
     L.check(L.lib().ia_broyden_stats(L.i32(1), L.i64(points.shape[0]), L.i32(I), L.ptr(points), L.ptr(dfm.voxel_J_cl), L.i32(1), L.i32(D), L.i32(H),
