@@ -201,12 +201,19 @@ __device__ __forceinline__ uint32_t level_index(uint32_t hsize, uint32_t res, ui
     return min(index >= hsize ? index - hsize : index, hsize - 1u);      // the clamp only bites for points outside the unit cube (redone below)
 }
 
-template <bool HASHED>
+// ONE_LOAD (the dense levels of the feature-only kernel; the Jacobian kernel keeps the load pairs above): on a dense level
+// i1 = i0 + 1, so ONE 16-byte load at tab + i0 (8-byte aligned) is the whole x-pair -- no aligned-pair select, no i1 load: 4
+// instead of 8 lane-loads per point and level where every one of them hits the L1 and the look-up rate is what binds.
+// Two exceptions join the redo of the points outside the cube: i0 is the table's last entry, whose x-neighbour wraps to entry 0
+// (a cell on an upper face, where the index passes the table size), or the clamp of level_index() bit.  The load itself stays
+// inside the table either way.
+template <bool HASHED, bool ONE_LOAD>
 __device__ __forceinline__ void xcd_gather2(const float2* __restrict__ tab, uint32_t hsize, uint32_t res, float sc, const float xa[3],
                                             const float xb[3], float2 va[8], float2 vb[8], float pa[3], float pb[3])
 {
     typedef float v2f __attribute__((ext_vector_type(2)));
     typedef float f4_a16 __attribute__((ext_vector_type(4), aligned(16)));
+    static_assert(!(HASHED && ONE_LOAD), "the x-neighbours of a hashed level are adjacent entries for even x only");
     uint32_t ga[3], gb[3];
 #pragma unroll
     for (int d = 0; d < 3; d++) {
@@ -215,37 +222,57 @@ __device__ __forceinline__ void xcd_gather2(const float2* __restrict__ tab, uint
         const float p2 = fmaf(sc, xb[d], 0.5f), fl2 = floorf(p2);
         gb[d] = (uint32_t)(int)fl2; pb[d] = p2 - fl2;
     }
-    uint32_t i0[8], i1[8];
+    bool last_a = false, last_b = false;
+    if (ONE_LOAD) {
+        uint32_t i0[8];
 #pragma unroll
-    for (int c = 0; c < 4; c++) {
-        i0[c] = level_index<HASHED>(hsize, res, ga[0], ga[1] + (c & 1), ga[2] + ((c >> 1) & 1));
-        i1[c] = level_index<HASHED>(hsize, res, ga[0] + 1u, ga[1] + (c & 1), ga[2] + ((c >> 1) & 1));
-        i0[4 + c] = level_index<HASHED>(hsize, res, gb[0], gb[1] + (c & 1), gb[2] + ((c >> 1) & 1));
-        i1[4 + c] = level_index<HASHED>(hsize, res, gb[0] + 1u, gb[1] + (c & 1), gb[2] + ((c >> 1) & 1));
-    }
-    f4_a16 q[8];
-    v2f t[8];
+        for (int c = 0; c < 4; c++) {
+            i0[c] = level_index<false>(hsize, res, ga[0], ga[1] + (c & 1), ga[2] + ((c >> 1) & 1));
+            i0[4 + c] = level_index<false>(hsize, res, gb[0], gb[1] + (c & 1), gb[2] + ((c >> 1) & 1));
+        }
+        f4_a8b q[8];
 #pragma unroll
-    for (int c = 0; c < 8; c++) {
-        q[c] = *reinterpret_cast<const f4_a16*>(tab + (i0[c] & ~1u));
-        t[c] = *reinterpret_cast<const v2f*>(tab + i1[c]);
-    }
+        for (int c = 0; c < 8; c++) q[c] = *reinterpret_cast<const f4_a8b*>(tab + min(i0[c], hsize - 2u));
 #pragma unroll
-    for (int c = 0; c < 8; c++) {
-        const bool odd = (i0[c] & 1u) != 0u;
-        const float2 lo = make_float2(q[c].x, q[c].y), hi = make_float2(q[c].z, q[c].w);
-        const float2 e0 = odd ? hi : lo;
-        const float2 e1 = (i1[c] == (i0[c] ^ 1u)) ? (odd ? lo : hi) : make_float2(t[c].x, t[c].y);
-        if (c < 4) { va[2 * c] = e0; va[2 * c + 1] = e1; } else { vb[2 * (c - 4)] = e0; vb[2 * (c - 4) + 1] = e1; }
+        for (int c = 0; c < 4; c++) {
+            va[2 * c] = make_float2(q[c].x, q[c].y); va[2 * c + 1] = make_float2(q[c].z, q[c].w);
+            vb[2 * c] = make_float2(q[4 + c].x, q[4 + c].y); vb[2 * c + 1] = make_float2(q[4 + c].z, q[4 + c].w);
+        }
+        last_a = max(max(i0[0], i0[1]), max(i0[2], i0[3])) >= hsize - 1u;
+        last_b = max(max(i0[4], i0[5]), max(i0[6], i0[7])) >= hsize - 1u;
+    } else {
+        uint32_t i0[8], i1[8];
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            i0[c] = level_index<HASHED>(hsize, res, ga[0], ga[1] + (c & 1), ga[2] + ((c >> 1) & 1));
+            i1[c] = level_index<HASHED>(hsize, res, ga[0] + 1u, ga[1] + (c & 1), ga[2] + ((c >> 1) & 1));
+            i0[4 + c] = level_index<HASHED>(hsize, res, gb[0], gb[1] + (c & 1), gb[2] + ((c >> 1) & 1));
+            i1[4 + c] = level_index<HASHED>(hsize, res, gb[0] + 1u, gb[1] + (c & 1), gb[2] + ((c >> 1) & 1));
+        }
+        f4_a16 q[8];
+        v2f t[8];
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+            q[c] = *reinterpret_cast<const f4_a16*>(tab + (i0[c] & ~1u));
+            t[c] = *reinterpret_cast<const v2f*>(tab + i1[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < 8; c++) {
+            const bool odd = (i0[c] & 1u) != 0u;
+            const float2 lo = make_float2(q[c].x, q[c].y), hi = make_float2(q[c].z, q[c].w);
+            const float2 e0 = odd ? hi : lo;
+            const float2 e1 = (i1[c] == (i0[c] ^ 1u)) ? (odd ? lo : hi) : make_float2(t[c].x, t[c].y);
+            if (c < 4) { va[2 * c] = e0; va[2 * c + 1] = e1; } else { vb[2 * (c - 4)] = e0; vb[2 * (c - 4) + 1] = e1; }
+        }
     }
     if (!HASHED) {
         // a point outside the unit cube (a candidate of the search outside the field's box) has wrapped cell coordinates: its
         // index needs the full modulo of grid_index(), as tiny-cuda-nn computes it.  Rare and divergent: redone here, after the
         // loads of the common case.
-        if (ga[0] > res || ga[1] > res || ga[2] > res)
+        if (last_a || ga[0] > res || ga[1] > res || ga[2] > res)
 #pragma unroll
             for (int c = 0; c < 8; c++) va[c] = tab[grid_index(hsize, res, ga[0] + (c & 1), ga[1] + ((c >> 1) & 1), ga[2] + ((c >> 2) & 1))];
-        if (gb[0] > res || gb[1] > res || gb[2] > res)
+        if (last_b || gb[0] > res || gb[1] > res || gb[2] > res)
 #pragma unroll
             for (int c = 0; c < 8; c++) vb[c] = tab[grid_index(hsize, res, gb[0] + (c & 1), gb[1] + ((c >> 1) & 1), gb[2] + ((c >> 2) & 1))];
     }
@@ -316,8 +343,8 @@ __global__ __launch_bounds__(THREADS) void hash_fwd_xcd_kernel(int64_t n, const 
             // grid_index()'s rule for this level (wave-uniform): dense while res^3 fits the table, else hashed (power-of-two table)
             const uint64_t r64 = res;
             const bool hashed = r64 * r64 * r64 > (uint64_t)hsize;
-            if (plan.straight && hashed && (hsize & (hsize - 1u)) == 0u) xcd_gather2<true>(tab, hsize, res, sc, xa, xb, va, vb, pa, pb);
-            else if (plan.straight && !hashed) xcd_gather2<false>(tab, hsize, res, sc, xa, xb, va, vb, pa, pb);
+            if (plan.straight && hashed && (hsize & (hsize - 1u)) == 0u) xcd_gather2<true, false>(tab, hsize, res, sc, xa, xb, va, vb, pa, pb);
+            else if (plan.straight && !hashed) xcd_gather2<false, !WITH_JAC>(tab, hsize, res, sc, xa, xb, va, vb, pa, pb);
             else {
                 xcd_gather<WITH_JAC>(tab, hsize, res, sc, xa, va, pa);
                 xcd_gather<WITH_JAC>(tab, hsize, res, sc, xb, vb, pb);
