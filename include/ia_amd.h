@@ -350,7 +350,12 @@ int ia_hashgrid_bwd(int64_t n, const float* x, int n_levels, int n_features, int
 /* same result (up to fp32 summation order) without the fabric atomics: multisplit of the (index, value) records into
  * (level, 8192-entry slice) buckets + LDS reduction per bucket in 64-bit fixed point with integer atomics (exact,
  * order-independent sums of values quantised to 2^-40 of the level's largest |value|; see csrc/hashgrid.hip).  scratch: device buffer of
- * ia_hashgrid_bwd_scratch_bytes(n, ...) bytes (~1.3 KB per point); n * n_levels * 8 must be < 2^31. */
+ * ia_hashgrid_bwd_scratch_bytes(n, ...) bytes (~1.3 KB per point); n * n_levels * 8 must be < 2^31.
+ * LIMIT: no level may have more than 64 slices, i.e. more than 2^19 table entries (log2_hashmap_size <= 19), and the slices of
+ * all levels together are at most 1024.  For any other configuration ia_hashgrid_bwd_scratch_bytes returns -1 and
+ * ia_hashgrid_bwd_binned returns the invalid-argument status before it enqueues anything; ia_hashgrid_bwd has no such limit.
+ * A level whose gradient rows hold a +-inf is left as it was (its fixed-point scale would be meaningless); the other levels
+ * are not affected. */
 int64_t ia_hashgrid_bwd_scratch_bytes(int64_t n, int n_levels, int log2_hashmap_size, int base_resolution,
                                       float per_level_scale);
 int ia_hashgrid_bwd_binned(int64_t n, const float* x, int n_levels, int n_features, int log2_hashmap_size,

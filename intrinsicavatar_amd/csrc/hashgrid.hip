@@ -511,6 +511,17 @@ __host__ void make_bins(BinCfg& b, const HashCfg& c)
     b.n_buckets = k;
 }
 
+// what the binned kernels can take: the staged fill gives one LANE to each slice of a level (`lane < nb`, UnitLds::cur[64]), so a
+// level has at most 64 slices (a table of at most 2^19 entries per level), and the count histogram holds MAX_BUCKETS buckets
+constexpr int MAX_LEVEL_SLICES = 64;
+__host__ bool bins_supported(const BinCfg& b, int n_levels)
+{
+    if (b.n_buckets > MAX_BUCKETS) return false;
+    for (int l = 0; l < n_levels; l++)
+        if (b.bstart[l + 1] - b.bstart[l] > MAX_LEVEL_SLICES) return false;
+    return true;
+}
+
 // running maximum of a level's |record value| (scale of the fixed-point reduction).  Every wave used to fire one
 // device-scope atomicMax per level at the SAME address: ~400 k same-address atomics serialise at the memory side and
 // cost 1.7 - 3.5 ms per launch (measured by ablation).  The maximum converges after a few waves, so look first (a stale
@@ -1203,7 +1214,7 @@ IA_EXPORT int64_t ia_hashgrid_bwd_scratch_bytes(int64_t n, int n_levels, int log
     make_cfg(c, n_levels, log2_hashmap_size, base_resolution, per_level_scale);
     BinCfg b;
     make_bins(b, c);
-    if (b.n_buckets > MAX_BUCKETS) return -1;
+    if (!bins_supported(b, n_levels)) return -1;
     BinLayout L;
     return (int64_t)bin_layout(nullptr, SIZE_MAX, n, n_levels, b.n_buckets, &L);
 }
@@ -1224,6 +1235,7 @@ IA_EXPORT int ia_hashgrid_bwd_binned(int64_t n, const float* x, int n_levels, in
     BinCfg b;
     make_bins(b, c);
     IA_REQUIRE(b.n_buckets <= MAX_BUCKETS, "too many (level, slice) buckets");
+    IA_REQUIRE(bins_supported(b, n_levels), "a level has more than 64 slices of 8192 entries (log2_hashmap_size > 19): use ia_hashgrid_bwd");
     BinLayout L;
     bin_layout(scratch, scratch_bytes > 0 ? (size_t)scratch_bytes : 0, n, n_levels, b.n_buckets, &L);       // (a negative size fits nothing)
     IA_REQUIRE(scratch != nullptr && L.fits, "scratch smaller than ia_hashgrid_bwd_scratch_bytes(n)");

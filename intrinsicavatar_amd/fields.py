@@ -67,8 +67,18 @@ def hashgrid_backward(x01: Tensor, g_enc: Optional[Tensor], grad_params: Tensor,
     """accumulate d L / d table into grad_params (see include/ia_amd.h ia_hashgrid_bwd / ia_hashgrid_bwd_binned).
     method: None (by batch size) | 'atomic' | 'binned'."""
     n = x01.shape[0]
-    method = method or ("binned" if n >= HASH_BWD_BINNED_MIN else "atomic")
     cargs = (cfg["n_levels"], cfg["n_features_per_level"], cfg["log2_hashmap_size"], cfg["base_resolution"], cfg["per_level_scale"])
+    if method is None and n < HASH_BWD_BINNED_MIN:
+        method = "atomic"
+    if method != "atomic":
+        # the binned path takes tables of at most 64 slices per level (include/ia_amd.h): its size query answers -1 for any other
+        binned_ok = int(L.lib().ia_hashgrid_bwd_scratch_bytes(min(n, HASH_BWD_CHUNK), cfg["n_levels"], cfg["log2_hashmap_size"],
+                                                              cfg["base_resolution"], cfg["per_level_scale"])) >= 0
+        if method == "binned" and not binned_ok:
+            raise L.IaError("hashgrid_backward(method='binned'): this table configuration is outside the binned path's limits "
+                            "(a level of more than 64 slices of 8192 entries); use method='atomic' or None")
+        if method is None:
+            method = "binned" if binned_ok else "atomic"
     if method == "atomic":
         L.lib().ia_hashgrid_bwd(n, x01, *cargs, g_enc, g_enc.stride(0) if g_enc is not None else 0, g_jac,
                                 g_jac.stride(0) if g_jac is not None else 0, q, grad_params)

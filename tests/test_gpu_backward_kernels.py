@@ -6,6 +6,9 @@ kernel is called through the route the training step uses (the torch.autograd.Fu
 tests/backward_refs.py by the rule stated there:  max|got - ref64| <= max(16 * e32, 32 ulp of max|ref64|),  e32 = the error of
 the same formula in fp32 on the CPU.  Pure copies / masks / gathers are compared with torch.equal.
 
+The hash-grid TABLE backward (ia_hashgrid_bwd, ia_hashgrid_bwd_binned) is not here: its home is tests/test_gpu_hash_bwd_kernels.py
+(same rule, applied per level; reference in tests/hash_bwd_refs.py).  This file stops at ia_hashgrid_jac_contract.
+
 Measured on the MI355X (err = max|got - ref64|, e32 = max|twin32 - ref64|; the largest err/e32 per kernel and quantity over all
 cases of this file, as backward_refs.format_table() prints it when the module's fixture is torn down):
 

@@ -1,5 +1,10 @@
 """GPU: neural-field kernels (hash grid, SH, fused MFMA MLPs) vs the CPU oracle / reference modules.
-Floating-point kernels => tolerance (stated per test); fp32 everywhere (reference: trainer.precision 32)."""
+Floating-point kernels => tolerance (stated per test); fp32 everywhere (reference: trainer.precision 32).
+
+The three hash-grid table backward tests here (test_hashgrid_bwd_vs_oracle, test_hashgrid_bwd_binned_equals_atomic_scatter,
+test_hashgrid_second_order_bwd_vs_autograd) are whole-table smoke checks at the product's configuration; the per-level, per-path
+comparison with an fp64 reference (other level counts and table sizes, points outside the cube, strides, masks, split buckets,
+scratch bounds) is tests/test_gpu_hash_bwd_kernels.py."""
 import os
 
 import numpy as np
