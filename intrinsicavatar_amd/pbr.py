@@ -619,6 +619,26 @@ _FLAG_SLOT = {}          # id(src) -> (src, flag, slot) of the last few secondar
 
 
 @torch.no_grad()
+def light_rays(vi, normals: Tensor, emitter, w2s_rot: Tensor, render_mode: str, spp: int, light_u: Optional[Tensor],
+               shuffle_u: Optional[Tensor], light_sampling: str = "shared"):
+    """secondary rays of the light / uniform_light estimators at the foreground re-samples of `vi` (normals [F,3]: their gathered normals).
+    'light': emitter.sample rotated to SMPL space; 'shared' (eval, :777-786) = spp directions per frame (:292-305) permuted per ray
+    (:1356-1378), 'per_point' (training, :772-776) = one per point from light_u [>= F,3] or None.  'uniform_light': the stratified
+    uniform sphere (:680-689) as-is in SMPL space, permuted per ray.  returns (rays_o, rays_d, src, out_dirs, inv_pdf | None, shuffled | None)."""
+    if render_mode == "light" and light_sampling == "per_point":
+        u = light_u[:vi.F].contiguous() if light_u is not None else None
+        return (*secondary_rays(normals, vi.positions, emitter.sample(vi.F, u, w2s_rot=w2s_rot)), None, None)
+    if render_mode == "light":
+        dirs_smpl, inv_pdf_all = emitter.sample(spp, light_u, w2s_rot=w2s_rot), None
+    else:
+        assert spp == 512, "uniform_light asserts samples_per_pixel == 512 (:1392)"
+        dirs_smpl, inv_pdf_all = uniform_sphere_stratified(16, 32, light_u[:, :2])
+    shuffled = vi.shuffle(shuffle_u)
+    rays = secondary_rays(normals, vi.positions, dirs_smpl, dir_index=shuffled)
+    return (*rays, inv_pdf_all[shuffled.long()] if inv_pdf_all is not None else None, shuffled)
+
+
+@torch.no_grad()
 def scatter_secondary(F_: int, src: Tensor, tr: Tensor, rgb: Tensor):
     """traced (transmittance [M,1], rgb [M,3]) back into dense [F,1] / [F,3] (zeros for masked points), transmittance
     clamped to [0, 1] (:796-803).  With the (flag, slot) of the secondary_rays call that made `src` at hand every dense element is written

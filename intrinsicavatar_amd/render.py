@@ -14,6 +14,7 @@ stratified near plane.  All heavy work is in libia_amd.so; torch is used for all
 boolean-mask bookkeeping between the operators (exactly where the reference uses it).
 """
 import os
+import threading
 from typing import Dict, Optional
 
 import torch
@@ -23,6 +24,9 @@ from . import _lib as L
 from . import lib_nerfacc, nerfacc
 from .deformer import SNARFDeformer
 from .nerfacc import RayIntervals
+
+
+LOSS_MAPS = ("normals_orientation_loss_map", "albedo_smoothness_loss_map", "roughness_smoothness_loss_map", "metallic_smoothness_loss_map")
 
 
 def ray_points(rays_o: Tensor, rays_d: Tensor, ray_indices: Tensor, t0: Tensor, t1: Optional[Tensor] = None) -> Tensor:
@@ -78,6 +82,22 @@ def plan_secondary_chunks(M: int, chunk: int, n_streams: int = 1, min_chunk: int
 class RenderStep:
     """One frame's render_step.  `occ_binaries` [1,64,64,64] bool + `occ_aabb` [1,6] = the (test-time)
     occupancy grid of the frame (prepare_test_occupancy_grid, intrinsic_avatar.py:360-381)."""
+    SORT_MIN_POINTS = 1 << 20
+    SORT_DROP_BITS = 0            # low Morton bits left unsorted (0, 3 or 6)
+    # points per deformer search: P * 13 (point, init) items must stay below 2^31 (165.2 M points) and x / valid take 169 B per
+    # point (25 GB at 150 M); the headline step's 16 Mi-ray secondary chunks average 145 M sample points
+    MAX_SEARCH_POINTS = int(os.environ.get("IA_MAX_SEARCH_POINTS", str(150_000_000)))
+    SECONDARY_STREAMS = int(os.environ.get("IA_SECONDARY_STREAMS", "2"))
+    STREAM_FALLBACK_COOLDOWN = 64
+    # bytes of device memory a marched ray of a chunk keeps live at the peak of its chunk on the headline scene (9 samples per ray on
+    # average x (search outputs + sorted copies + level-major hash features)): 142 GiB live for 2 x 10.5 Mi rays = ~7 KB per ray
+    SECONDARY_BYTES_PER_RAY = int(os.environ.get("IA_SECONDARY_BYTES_PER_RAY", "7168"))
+    # below ~8 M rays the kernels of a chunk no longer fill the device and splitting them makes it worse (config-4 shape, 1 M secondary rays:
+    # 21.8 ms per step serial, 24.2 on two streams)
+    SECONDARY_STREAMS_MIN_RAYS = int(os.environ.get("IA_SECONDARY_STREAMS_MIN_RAYS", str(1 << 23)))
+    SECONDARY_MIN_CHUNK = int(os.environ.get("IA_SECONDARY_MIN_CHUNK", str(1 << 22)))
+    _CONST = {}
+    _march_hooks = threading.local()        # per host thread: .enter (callable) / .streams (override of SECONDARY_STREAMS)
 
     def __init__(self, geometry, radiance, density, deformer: SNARFDeformer, occ_binaries: Tensor, occ_aabb: Tensor,
                  render_step_size: float, importance_sample: bool = True):
@@ -97,11 +117,18 @@ class RenderStep:
         return self._grid_bits[1]
 
     # ------------------------------------------------------------------ helpers
+    @staticmethod
+    def _sort_points() -> bool:
+        """IA_SORT_POINTS, read at call time (tests switch it per test)."""
+        return os.environ.get("IA_SORT_POINTS", "1") == "1"
+
+    @staticmethod
+    def _background(background_color: Optional[Tensor], dev) -> Tensor:
+        return torch.ones(3, device=dev) if background_color is None else background_color
+
     def _beta(self) -> Tensor:
         d = self.density
         return d.beta_value() if hasattr(d, "beta_value") else d.get_beta().detach().reshape(1).float().contiguous()
-
-    _CONST = {}
 
     @classmethod
     def _const(cls, value: float, n: int, dev) -> Tensor:
@@ -112,13 +139,6 @@ class RenderStep:
         if t is None or t.shape[0] < n:
             t = cls._CONST[key] = torch.full((max(n + n // 4, 4096),), float(value), device=dev)
         return t[:n]
-
-    SORT_MIN_POINTS = 1 << 20
-    # points per deformer search: P * 13 (point, init) items must stay below 2^31 (165.2 M points) and x / valid take 169 B per
-    # point (25 GB at 150 M); the headline step's 16 Mi-ray secondary chunks average 145 M sample points
-    MAX_SEARCH_POINTS = int(os.environ.get("IA_MAX_SEARCH_POINTS", str(150_000_000)))
-
-    SORT_DROP_BITS = 0     # low Morton bits left unsorted (0, 3 or 6)
 
     def _sort_grid_params(self):
         """(origin, 1 / cell) of the Morton grid of _spatial_order, cached per occupancy box (ONE attribute assignment: several host threads
@@ -159,7 +179,7 @@ class RenderStep:
             # the search keeps x [P,13,3] + valid [P,13] (169 B / point) and its packing needs P * 13 < 2^31: bound the batch in
             # POINTS, whatever the caller's ray chunk produced (a dense occupancy grid gives 64 samples per secondary ray)
             return torch.cat([self._sdf_at(pts[a:a + self.MAX_SEARCH_POINTS]) for a in range(0, n, self.MAX_SEARCH_POINTS)])
-        if n < self.SORT_MIN_POINTS or os.environ.get("IA_SORT_POINTS", "1") != "1":
+        if n < self.SORT_MIN_POINTS or not self._sort_points():
             return self.deformer.deform_sdf(pts, self.geometry)
         # the search reads the points THROUGH the permutation and the min-select writes through it: no gathered copy of the points
         # (the 12-byte random gather dragged 64-byte sectors: 4.7 x its algorithmic bytes, profiles/r02_pmc_traffic.json)
@@ -215,19 +235,24 @@ class RenderStep:
         return rays_o, rays_d, far, t_starts, t_ends, ray_indices, packed_info, stats
 
     # ------------------------------------------------------------------ forward (eval)
+    def _shade(self, pts: Tensor, rays_d: Tensor, ray_indices: Tensor, w2s_rot: Optional[Tensor], alpha_of, **radiance_kw):
+        """no-grad callers' shading of a sample list: deform, normals, alpha_of(sdf) (the caller's alpha entry point), radiance.
+        w2s_rot None: made here, after the deformer.  returns (deform() result, normal_smpl, normal_world, alphas, radiance result)."""
+        d = self.deformer.deform(pts, self.geometry, with_grad=True, with_feature=True)
+        if w2s_rot is None:
+            w2s_rot = self.deformer.w2s[:3, :3].contiguous()
+        normal_smpl, normal_world, refl01 = shade_prep(d["sdf_grad"], rays_d, ray_indices, w2s_rot)
+        alphas = alpha_of(d["sdf"])
+        return d, normal_smpl, normal_world, alphas, self.radiance(d["pts_cano"], d["feature"], refl01, normal_world, **radiance_kw)
+
     @torch.no_grad()
     def forward(self, rays: Tensor, jitter: Optional[Tensor] = None) -> Dict[str, Tensor]:
-        dfm = self.deformer
         rays_o, rays_d, far, t_starts, t_ends, ray_indices, packed_info, stats = self.sample(rays, jitter)
         beta = self._beta()
         # -- 5. shade + composite (rgb_normal_alpha_fn + rendering_with_normals_sdf)
         pts = ray_points(rays_o, rays_d, ray_indices, t_starts, t_ends)
-        d = dfm.deform(pts, self.geometry, with_grad=True, with_feature=True)
-        w2s_rot = dfm.w2s[:3, :3].contiguous()
-        normal_smpl, normal_world, refl01 = shade_prep(d["sdf_grad"], rays_d, ray_indices, w2s_rot)
-        dists = t_ends - t_starts
-        alphas = laplace_alpha(d["sdf"], dists, beta)
-        rgbs = self.radiance(d["pts_cano"], d["feature"], refl01, normal_world)
+        d, normal_smpl, normal_world, alphas, rgbs = self._shade(pts, rays_d, ray_indices, None,
+                                                                 lambda sdf: laplace_alpha(sdf, t_ends - t_starts, beta))
         weights, trans = nerfacc.render_weight_from_alpha(alphas, packed_info=packed_info)
         acc = lambda v: nerfacc._Accumulate.apply(weights, v, ray_indices, packed_info)      # noqa: E731
         colors, normals, opac = acc(rgbs), acc(normal_world), acc(None)
@@ -294,9 +319,8 @@ class RenderStep:
             den = eik_denominator(int(t_starts.shape[0])) if callable(eik_denominator) else eik_denominator
             loss = train_phys.training_loss_phys(out, target_rgb, target_mask, **({} if den is None else dict(eik_denominator=den)))
         else:
-            if background_color is None:
-                background_color = torch.ones(3, device=rays.device)
-            d = self._training_dict(out, rays.shape[0], far, t_starts, t_ends, ray_indices, packed_info, background_color, render_mode)
+            d = self._training_dict(out, rays.shape[0], far, t_starts, t_ends, ray_indices, packed_info,
+                                    self._background(background_color, rays.device), render_mode)
             loss, out["loss_terms"] = train_phys.reference_training_loss(d, target_rgb, target_mask, loss_config, material)
             out["output_dict"] = d
         (loss * loss_scale if loss_scale != 1.0 else loss).backward(retain_graph=retain_graph)
@@ -339,8 +363,17 @@ class RenderStep:
         args = (rays_o, rays_d, near, far, step, beta, w2s_rot, tr, rgb)
         if n_streams <= 1 or len(work) <= 1:
             self._secondary_chunks(work, *args)
-            return tr, rgb
-        import threading
+        elif not self._secondary_chunks_on_streams(work[::-1], n_streams, args):
+            # march again on the caller's stream, one chunk at a time (same results: chunking-invariant)
+            tr.fill_(1.0)
+            rgb.zero_()
+            self._secondary_chunks(plan_secondary_chunks(M, chunk, 1)[::-1], *args)
+        return tr, rgb
+
+    def _secondary_chunks_on_streams(self, chunks, n_streams: int, args) -> bool:
+        """_secondary_chunks(chunks, *args) on n_streams host threads, each on its own HIP stream.  False: the side streams' allocator
+        pools ran out of memory, their blocks are given back and the caller marches again."""
+        dev = args[0].device
         _ = self.grid_bits, self._sort_grid_params()            # lazily cached host-side state: made before the threads start
         main = torch.cuda.current_stream(dev)
         if getattr(self, "_side_streams", None) is None or len(self._side_streams) != n_streams or self._side_streams[0].device != dev:
@@ -349,7 +382,6 @@ class RenderStep:
         # STATIC assignment, chunk j to thread j mod n: every thread sees the same chunk sizes step after step, so its stream's allocator
         # pool holds the right blocks after one warm-up (with a shared queue the thread that happened to get the short last chunk in the
         # warm-up paid a multi-GB hipMalloc later: 0.245 ... 0.405 s per relit frame, run to run)
-        chunks = work[::-1]
         works = [chunks[k::n_streams][::-1] for k in range(n_streams)]
 
         def worker(side, my_work):
@@ -375,7 +407,7 @@ class RenderStep:
         if errors:
             if all(isinstance(e, torch.cuda.OutOfMemoryError) for e in errors):
                 # the side streams' allocator pools did not fit after all (another process on the GPU, a smaller device): give their
-                # blocks back and march the batch again on the caller's stream, one chunk at a time -- same results, chunking-invariant
+                # blocks back
                 del errors[:]
                 self._side_streams = None
                 torch.cuda.synchronize(dev)
@@ -384,20 +416,9 @@ class RenderStep:
                 # the gate let this batch through and it did not fit: do not try again on the next calls (each failed attempt costs a
                 # full synchronise, an empty_cache and a second march); the streams come back after STREAM_FALLBACK_COOLDOWN marches
                 self._stream_cooldown = self.STREAM_FALLBACK_COOLDOWN
-                tr.fill_(1.0)
-                rgb.zero_()
-                self._secondary_chunks(plan_secondary_chunks(M, chunk, 1)[::-1], *args)
-                return tr, rgb
+                return False
             raise errors[0]
-        return tr, rgb
-
-    import threading as _threading
-    _march_hooks = _threading.local()          # per host thread: .enter (callable) / .streams (override of SECONDARY_STREAMS)
-    SECONDARY_STREAMS = int(os.environ.get("IA_SECONDARY_STREAMS", "2"))
-    STREAM_FALLBACK_COOLDOWN = 64
-    # bytes of device memory a marched ray of a chunk keeps live at the peak of its chunk on the headline scene (9 samples per ray on
-    # average x (search outputs + sorted copies + level-major hash features)): 142 GiB live for 2 x 10.5 Mi rays = ~7 KB per ray
-    SECONDARY_BYTES_PER_RAY = int(os.environ.get("IA_SECONDARY_BYTES_PER_RAY", "7168"))
+        return True
 
     def _secondary_streams_for(self, M: int, chunk: int, dev) -> int:
         """how many HIP streams / host threads the secondary march of M rays takes.  Each side stream has its own caching-allocator pool
@@ -437,10 +458,6 @@ class RenderStep:
             n = n if free + side >= need else 1
         self.last_secondary_streams = n
         return n
-    # below ~8 M rays the kernels of a chunk no longer fill the device and splitting them makes it worse (config-4 shape, 1 M secondary rays:
-    # 21.8 ms per step serial, 24.2 on two streams)
-    SECONDARY_STREAMS_MIN_RAYS = int(os.environ.get("IA_SECONDARY_STREAMS_MIN_RAYS", str(1 << 23)))
-    SECONDARY_MIN_CHUNK = int(os.environ.get("IA_SECONDARY_MIN_CHUNK", str(1 << 22)))
 
     def _secondary_chunks(self, work, rays_o, rays_d, near, far, step, beta, w2s_rot, tr, rgb):
         """works the chunks of `work` (this thread's own list, last one first) into tr / rgb."""
@@ -473,7 +490,7 @@ class RenderStep:
             # rendering(rgb_alpha_fn) (:430-456, volrend.py:19-194)
             pts = ray_points(ro, rd, ray_indices, t_starts, t_ends)
             np_ = pts.shape[0]
-            if np_ >= self.SORT_MIN_POINTS and os.environ.get("IA_SORT_POINTS", "1") == "1":
+            if np_ >= self.SORT_MIN_POINTS and self._sort_points():
                 # the shading points of a chunk in spatial order as well (search, hash gathers with Jacobian, both field heads;
                 # 1.5 ns -> 1.1 ns per point in the search): per-point work is order-free, only alpha and rgb go back to ray order
                 order = self._spatial_order(pts)
@@ -481,18 +498,13 @@ class RenderStep:
                 L.lib().ia_gather_rows3_i32(np_, pts, order, ps)
                 ol = order.long()
                 ri_s, dt_s = ray_indices[ol], (t_ends - t_starts)[ol]
-                d = self.deformer.deform(ps, self.geometry, with_grad=True, with_feature=True)
-                _, normal_world, refl01 = shade_prep(d["sdf_grad"], rd, ri_s, w2s_rot)
-                a_s = laplace_alpha(d["sdf"], dt_s, beta)
-                rgbs_s = self.radiance(d["pts_cano"], d["feature"], refl01, normal_world).contiguous()
+                *_, a_s, rgbs_s = self._shade(ps, rd, ri_s, w2s_rot, lambda sdf: laplace_alpha(sdf, dt_s, beta))
+                rgbs_s = rgbs_s.contiguous()
                 a, rgbs = torch.empty_like(a_s), torch.empty_like(rgbs_s)
                 L.lib().ia_scatter_f32_i32(np_, a_s, order, a)
                 L.lib().ia_scatter_rows3_i32(np_, rgbs_s, order, rgbs)
             else:
-                d = self.deformer.deform(pts, self.geometry, with_grad=True, with_feature=True)
-                _, normal_world, refl01 = shade_prep(d["sdf_grad"], rd, ray_indices, w2s_rot)
-                a = laplace_alpha_intervals(d["sdf"], t_starts, t_ends, beta)
-                rgbs = self.radiance(d["pts_cano"], d["feature"], refl01, normal_world)
+                *_, a, rgbs = self._shade(pts, rd, ray_indices, w2s_rot, lambda sdf: laplace_alpha_intervals(sdf, t_starts, t_ends, beta))
             w, _ = nerfacc.render_weight_from_alpha(a, packed_info=pinfo)
             acc = nerfacc._Accumulate.apply(w, None, ray_indices, pinfo)
             torch.neg(acc, out=tr[c0:c0 + m])                     # tr = 1 - acc written in place: (-acc) + 1 is the same IEEE operation
@@ -516,20 +528,16 @@ class RenderStep:
         add_emitter (configs/config.yaml:58, :1319-1333, :1455-1490): background re-samples and rays without re-samples carry the
         emitter's radiance along the camera ray (emitter.background) instead of background_color; `visibility` stays without background."""
         from . import pbr
-        dfm = self.deformer
         rays_o, rays_d, far, t_starts, t_ends, ray_indices, packed_info, stats = self.sample(rays, jitter)
         n_rays = rays_o.shape[0]
         dev = rays_o.device
         beta = self._beta()
-        w2s_rot = dfm.w2s[:3, :3].contiguous()
-        if background_color is None:
-            background_color = torch.ones(3, device=dev)
+        w2s_rot = self.deformer.w2s[:3, :3].contiguous()
+        background_color = self._background(background_color, dev)
         # -- shade with materials (rgb_normal_mats_alpha_fn, :1066-1156)
         pts = ray_points(rays_o, rays_d, ray_indices, t_starts, t_ends)
-        d = dfm.deform(pts, self.geometry, with_grad=True, with_feature=True)
-        normal_smpl, normal_world, refl01 = shade_prep(d["sdf_grad"], rays_d, ray_indices, w2s_rot)
-        alphas = laplace_alpha_intervals(d["sdf"], t_starts, t_ends, beta)
-        rgbs, enc2, xp2 = self.radiance(d["pts_cano"], d["feature"], refl01, normal_world, return_embedding=True)
+        d, normal_smpl, normal_world, alphas, (rgbs, enc2, xp2) = self._shade(
+            pts, rays_d, ray_indices, w2s_rot, lambda sdf: laplace_alpha_intervals(sdf, t_starts, t_ends, beta), return_embedding=True)
         mats = material(enc2, xp2, d["feature"], self.radiance.prog.mask(self.radiance.global_step, dev))
         if albedo_align_ratio is not None:
             mats = torch.cat([mats[:, :3] * albedo_align_ratio.as_subclass(Tensor).to(mats).reshape(1, 3), mats[:, 3:]], dim=1)
@@ -562,18 +570,8 @@ class RenderStep:
                 pos, view = vi.positions, vi.view_dirs
                 ind = lambda c: c if global_illumination else None      # noqa: E731
                 if render_mode in ("light", "uniform_light"):
-                    if render_mode == "light":
-                        # light directions: sampled once per frame (prepare, :292-305), rotated to SMPL space
-                        # (transform_dirs_w2s), permuted per ray (:1356-1378)
-                        dirs_smpl = emitter.sample(spp, light_u, w2s_rot=w2s_rot)
-                        inv_pdf_all = None
-                    else:
-                        # stratified uniform sphere (:680-689); directions are used as-is in SMPL space
-                        assert spp == 512, "uniform_light asserts samples_per_pixel == 512 (:1392)"
-                        dirs_smpl, inv_pdf_all = pbr.uniform_sphere_stratified(16, 32, light_u[:, :2])
-                    shuffled = vi.shuffle(shuffle_u)
-                    ro, rd, src, out_dirs = pbr.secondary_rays(nrm, pos, dirs_smpl, dir_index=shuffled)
-                    inv_pdf = inv_pdf_all[shuffled.long()] if render_mode == "uniform_light" else None
+                    ro, rd, src, out_dirs, inv_pdf, shuffled = pbr.light_rays(vi, nrm, emitter, w2s_rot, render_mode, spp, light_u,
+                                                                              shuffle_u, "shared")
                     stats["n_secondary"] = int(ro.shape[0])
                     t_, c_ = self.compute_indirect_radiance(ro, rd)
                     sec_tr, sec_rgb = pbr.scatter_secondary(F_, src, t_, c_)
@@ -622,34 +620,39 @@ class RenderStep:
     @staticmethod
     def output_dict(o: Dict[str, Tensor], background_color: Tensor, render_mode: str, n_samples: int) -> Dict[str, Tensor]:
         """the dict IntrinsicAvatarModel.forward_ returns with enable_phys (models/intrinsic_avatar.py:1492-1651): the linear
-        maps, the constant-background dict (`*_bg`) and the composited sRGB dict (`*_full`), same keys / shapes / dtypes."""
+        maps, the constant-background dict (`*_bg`) and the composited sRGB dict (`*_full`), same keys / shapes / dtypes.
+        `o` without comp_rgb_phys: the radiance-field form; o["transmittance"]: 1 - opacity where the caller has it already."""
         from . import pbr
         acc = o["opacity"]
         n, dev = acc.shape[0], acc.device
         bgc = background_color.to(dev).float()
+        phys = "comp_rgb_phys" in o
         out = dict(comp_rgb=o["comp_rgb"], comp_normal=o["comp_normal"], opacity=acc, depth=o["depth"], rays_valid=acc > 0,
-                   rays_valid_phys=acc > 0, num_samples=torch.as_tensor([n_samples], dtype=torch.int32, device=dev),
-                   comp_rgb_phys=o["comp_rgb_phys"], comp_demod_phys=o["comp_demod_phys"], comp_albedo=o["albedo"],
-                   comp_metallic=o["metallic"], comp_roughness=o["roughness"])
-        if render_mode == "uniform_light":
-            out["visibility"] = o["visibility"]
-        for k in ("sdf_samples", "sdf_grad_samples", "sdf_laplace_samples", "weights", "points", "intervals", "ray_indices",
-                  "normals_orientation_loss_map", "albedo_smoothness_loss_map", "roughness_smoothness_loss_map", "metallic_smoothness_loss_map"):
+                   rays_valid_phys=acc > 0 if phys else torch.zeros_like(acc, dtype=torch.bool),
+                   num_samples=torch.as_tensor([n_samples], dtype=torch.int32, device=dev))
+        if phys:
+            out.update(comp_rgb_phys=o["comp_rgb_phys"], comp_demod_phys=o["comp_demod_phys"], comp_albedo=o["albedo"],
+                       comp_metallic=o["metallic"], comp_roughness=o["roughness"])
+            if render_mode == "uniform_light":
+                out["visibility"] = o["visibility"]
+        for k in ("sdf_samples", "sdf_grad_samples", "sdf_laplace_samples", "weights", "points", "intervals", "ray_indices", *LOSS_MAPS):
             if k in o:
                 out[k] = o[k]                                                              # training form (:1519-1597)
-        bgm = bgc.mean().reshape(1, 1).expand(n, 1)
+        bgm = bgc.mean().reshape(1, 1).expand(n, 1) if phys else None
         out_bg = dict(comp_rgb=bgc[None].expand(n, 3), num_samples=torch.zeros_like(out["num_samples"]),
-                      rays_valid=torch.zeros_like(out["rays_valid"]), rays_valid_phys=torch.zeros_like(out["rays_valid_phys"]),
-                      comp_albedo=torch.zeros((n, 3), device=dev), comp_metallic=bgm, comp_roughness=bgm)
-        T = 1.0 - acc
+                      rays_valid=torch.zeros_like(out["rays_valid"]), rays_valid_phys=torch.zeros_like(out["rays_valid_phys"]))
+        if phys:
+            out_bg.update(comp_albedo=torch.zeros((n, 3), device=dev), comp_metallic=bgm, comp_roughness=bgm)
+        T = o["transmittance"] if "transmittance" in o else 1.0 - acc
         out_full = dict(comp_rgb=pbr.rgb_to_srgb(out["comp_rgb"] + out_bg["comp_rgb"] * T).clamp(0, 1),
                         num_samples=out["num_samples"] + out_bg["num_samples"], rays_valid=out["rays_valid"] | out_bg["rays_valid"],
-                        rays_valid_phys=out["rays_valid_phys"] | out_bg["rays_valid_phys"],
-                        comp_rgb_phys=pbr.rgb_to_srgb(out["comp_rgb_phys"]).clamp(0, 1),
-                        comp_demod_phys=pbr.rgb_to_srgb(out["comp_demod_phys"]).clamp(0, 1),
-                        comp_albedo=out["comp_albedo"] + out_bg["comp_albedo"] * T,
-                        comp_metallic=out["comp_metallic"] + out_bg["comp_metallic"] * T,
-                        comp_roughness=out["comp_roughness"] + out_bg["comp_roughness"] * T)
+                        rays_valid_phys=out["rays_valid_phys"] | out_bg["rays_valid_phys"])
+        if phys:
+            out_full.update(comp_rgb_phys=pbr.rgb_to_srgb(out["comp_rgb_phys"]).clamp(0, 1),
+                            comp_demod_phys=pbr.rgb_to_srgb(out["comp_demod_phys"]).clamp(0, 1),
+                            comp_albedo=out["comp_albedo"] + out_bg["comp_albedo"] * T,
+                            comp_metallic=out["comp_metallic"] + out_bg["comp_metallic"] * T,
+                            comp_roughness=out["comp_roughness"] + out_bg["comp_roughness"] * T)
         return {**out, **{k + "_bg": v for k, v in out_bg.items()}, **{k + "_full": v for k, v in out_full.items()}}
 
     @torch.no_grad()
@@ -660,8 +663,7 @@ class RenderStep:
         """IntrinsicAvatarModel.forward_ in eval mode with enable_phys (models/intrinsic_avatar.py:950-1651): relight() + the
         reference's output dict.  Random tensors are explicit.  albedo_only / albedo_align_ratio: the two model
         switches of the reference's test step (relight()); add_emitter: model.add_emitter (relight())."""
-        if background_color is None:
-            background_color = torch.ones(3, device=rays.device)
+        background_color = self._background(background_color, rays.device)
         o = self.relight(rays, material, emitter, spp, light_u, shuffle_u, background_color=background_color,
                          global_illumination=global_illumination, jitter=jitter, render_mode=render_mode, scatter_u=scatter_u,
                          albedo_only=albedo_only, albedo_align_ratio=albedo_align_ratio, add_emitter=add_emitter)
@@ -677,8 +679,7 @@ class RenderStep:
         (from env_base when given, else the emitter's image) behind background re-samples and on empty rays.
         curv_u [n_samples,3]: uniforms of the curvature probe (model.with_curvature_loss); without it sdf_laplace_samples is zero."""
         from . import train_phys
-        if background_color is None:
-            background_color = torch.ones(3, device=rays.device)
+        background_color = self._background(background_color, rays.device)
         rays_o, rays_d, far, t_starts, t_ends, ray_indices, packed_info, stats = self.sample(rays, jitter)
         res = train_phys.shade_differentiable_phys(
             self, material, emitter, rays_o, rays_d, ray_indices, t_starts, t_ends, packed_info, spp, light_u, shuffle_u,
@@ -695,32 +696,17 @@ class RenderStep:
         the radiance-field maps of train.shade_differentiable in the reference's output dict -- no `*_phys` / material keys,
         rays_valid_phys all false, the four loss maps zero, `_bg` and `_full` with the sRGB image over the background colour.
         curv_u [n_samples,3]: uniforms of the curvature probe (model.with_curvature_loss); without it sdf_laplace_samples is zero."""
-        from . import pbr, train
-        if background_color is None:
-            background_color = torch.ones(3, device=rays.device)
+        from . import train
         rays_o, rays_d, far, t_starts, t_ends, ray_indices, packed_info, stats = self.sample(rays, jitter)
         n_samples = int(t_starts.shape[0])
         res = train.shade_differentiable(self, rays_o, rays_d, ray_indices, t_starts, t_ends, packed_info,
                                          curv_u=curv_u[:n_samples] if curv_u is not None else None)
-        acc = res["opacity"]
-        n, dev = acc.shape[0], acc.device
-        bgc = background_color.to(dev).float()
-        T = 1.0 - acc
-        z1 = torch.zeros((n, 1), device=dev)
-        out = dict(comp_rgb=res["comp_rgb"], comp_normal=res["comp_normal"], opacity=acc, depth=res["depth"].detach() + T.detach() * far[:, None],
-                   rays_valid=acc > 0, rays_valid_phys=torch.zeros_like(acc, dtype=torch.bool),
-                   num_samples=torch.as_tensor([n_samples], dtype=torch.int32, device=dev),
-                   sdf_samples=res["sdf"], sdf_grad_samples=res["sdf_grad"],
-                   sdf_laplace_samples=res["sdf_laplace"] if "sdf_laplace" in res else torch.zeros_like(res["sdf"]),
-                   weights=res["weights"], points=(t_starts + t_ends) / 2.0, intervals=t_ends - t_starts, ray_indices=ray_indices,
-                   normals_orientation_loss_map=z1, albedo_smoothness_loss_map=z1, roughness_smoothness_loss_map=z1,
-                   metallic_smoothness_loss_map=z1)
-        out_bg = dict(comp_rgb=bgc[None].expand(n, 3), num_samples=torch.zeros_like(out["num_samples"]),
-                      rays_valid=torch.zeros_like(out["rays_valid"]), rays_valid_phys=torch.zeros_like(out["rays_valid_phys"]))
-        out_full = dict(comp_rgb=pbr.rgb_to_srgb(out["comp_rgb"] + out_bg["comp_rgb"] * T).clamp(0, 1),
-                        num_samples=out["num_samples"] + out_bg["num_samples"], rays_valid=out["rays_valid"] | out_bg["rays_valid"],
-                        rays_valid_phys=out["rays_valid_phys"] | out_bg["rays_valid_phys"])
-        d = {**out, **{k + "_bg": v for k, v in out_bg.items()}, **{k + "_full": v for k, v in out_full.items()}}
+        T = 1.0 - res["opacity"]
+        o = dict(res, transmittance=T, depth=res["depth"].detach() + T.detach() * far[:, None], sdf_samples=res["sdf"],
+                 sdf_grad_samples=res["sdf_grad"], sdf_laplace_samples=res["sdf_laplace"] if "sdf_laplace" in res else torch.zeros_like(res["sdf"]),
+                 points=(t_starts + t_ends) / 2.0, intervals=t_ends - t_starts, ray_indices=ray_indices,
+                 **dict.fromkeys(LOSS_MAPS, torch.zeros((rays.shape[0], 1), device=rays.device)))
+        d = self.output_dict(o, self._background(background_color, rays.device), "light", n_samples)
         d["stats"] = dict(stats)
         return d
 
@@ -737,7 +723,7 @@ class RenderStep:
         z1 = torch.zeros((n_rays, 1), device=dev)
         o.update(sdf_samples=res["sdf"], sdf_grad_samples=res["sdf_grad"], sdf_laplace_samples=res["sdf_laplace"] if "sdf_laplace" in res else torch.zeros_like(res["sdf"]),
                  points=mid, intervals=t_ends - t_starts, ray_indices=ray_indices)
-        for k in ("normals_orientation_loss_map", "albedo_smoothness_loss_map", "roughness_smoothness_loss_map", "metallic_smoothness_loss_map"):
+        for k in LOSS_MAPS:
             o.setdefault(k, z1)
         if render_mode == "uniform_light":
             if "volume_interaction" in res and "visibility" not in o:

@@ -17,6 +17,7 @@ kernels (csrc/mlp_train.hip) reduce the weight gradients themselves; wgrad() is 
 dW = G^T A ([64 x n] x [n x <=68]; rocBLAS maps this shape to a single output tile walking K = millions of points).
 """
 import math
+from collections import namedtuple
 from typing import Dict, Optional
 
 import torch
@@ -269,58 +270,69 @@ def curvature_laplace(geo, pts_cano: Tensor, grad_c: Tensor, rand_u: Tensor, eps
     return torch.acos(dot.clamp(-1.0 + 1e-6, 1.0 - 1e-6)) / math.pi
 
 
-def shade_differentiable(rs, rays_o: Tensor, rays_d: Tensor, ray_indices: Tensor, t_starts: Tensor, t_ends: Tensor,
-                         packed_info: Tensor, curv_u: Optional[Tensor] = None) -> Dict[str, Tensor]:
-    """differentiable rgb_normal_alpha_fn + rendering_with_normals_sdf for the samples found by the no-grad pass.
-    curv_u [n_samples,3]: uniforms for the curvature probe directions (enables out["sdf_laplace"])."""
-    dfm, geo, rad = rs.deformer, rs.geometry, rs.radiance
-    n_rays = packed_info.shape[0]
+# d: the no-grad deform() result; pts_cano: d's, or with the pose terms; geo_w: this step's geo.effective_weights(); J_inv_win: pose terms only
+ShadeFront = namedtuple("ShadeFront", "d pts_cano feat sdf sdf_grad c2w grad_c valid normal_smpl normal_world refl01 alphas w2s_rot geo_w J_inv_win")
+
+
+def shade_front(rs, rays_o: Tensor, rays_d: Tensor, ray_indices: Tensor, t_starts: Tensor, t_ends: Tensor, level_bits,
+                pose_grad: bool) -> ShadeFront:
+    """differentiable front half of shade_differentiable and train_phys.shade_differentiable_phys: sample points, the no-grad
+    candidate search + winner selection, _SDFField on the winners, the normal push-forward, _ShadePrep and _Alpha.
+    level_bits(): the hash levels whose table rows take a gradient, asked once this step's level mask is made;
+    pose_grad: attach the implicit pose terms (dfm.tfs is being optimised)."""
+    dfm, geo = rs.deformer, rs.geometry
     pts = render.ray_points(rays_o, rays_d, ray_indices, t_starts, t_ends)
-    pose_grad = dfm.tfs.requires_grad and torch.is_grad_enabled()
     with torch.no_grad():
         d = dfm.deform(pts, geo, with_grad=False, with_feature=False, want_fwd=True, want_jinv=pose_grad)      # candidate search + winner selection (the gradient is evaluated once, on the winners, by _SDFField)
-        valid = d["valid"]
-        win = c2w = None         # win: flat (point, init) index of each sample's winning candidate (pose mode), or a flag
-        if d["n_candidates"] > 0:
-            win = True
-            if pose_grad:
-                win = d["cand_src"].long()[d["sel"].long().clamp(min=0)]
-                c2w = d["fwd_J"].reshape(-1, 3, 3)[win]
-    pts_cano = d["pts_cano"]
-    if pose_grad and win is not None:
+        valid, found = d["valid"], d["n_candidates"] > 0
+        pose = pose_grad and found
+        if pose:
+            win = d["cand_src"].long()[d["sel"].long().clamp(min=0)]      # flat (point, init) index of each sample's winning candidate
+            c2w = d["fwd_J"].reshape(-1, 3, 3)[win]
+    pts_cano, J_inv_win = d["pts_cano"], None
+    if pose:
         # pose_correction / SMPL parameters are being optimised (configs/config.yaml: pose_correction.enable_pose_correction):
         # the roots get their implicit-function derivative and the normal push-forward its blended-rotation derivative;
         # the forward VALUES stay the ones the search kernels produced.
         J_inv_win = d["J_inv"].reshape(-1, 3, 3)[win]
         pts_cano, R = dfm.implicit_pose_terms(pts_cano, J_inv_win, valid)
         c2w = c2w + (R - R.detach()) * valid[:, None, None].to(R.dtype)
-    W1k, b1, W2, b2 = geo.effective_weights()
-    out, grad_c = _SDFField.apply(pts_cano, geo.grid_params, W1k, b1, W2, b2, geo.center, geo.scale, geo.prog.level_bits(),
-                                  geo.inv_scale_host())
-    # invalid points: sdf 1e5, feature 0, gradient [0,0,1] (snarf_deformer.py:192-231)
-    if pose_grad and win is not None:          # c2w carries the pose graph: plain torch expressions
+    geo_w = geo.effective_weights()
+    out, grad_c = _SDFField.apply(pts_cano, geo.grid_params, *geo_w, geo.center, geo.scale, level_bits(), geo.inv_scale_host())
+    # invalid points: sdf 1e5, feature 0, gradient [0,0,1] (snarf_deformer.py:192-231); valid ones: the normal push-forward with the
+    # winning candidate's blended rotation
+    if pose:                                   # c2w carries the pose graph: plain torch expressions
         vf = valid[:, None].float()
         dflt_g = torch.tensor([0.0, 0.0, 1.0], device=pts.device)
         feat = out * vf
         sdf = torch.where(valid, out[:, 0], torch.full_like(out[:, 0], 1e5))
         sdf_grad = torch.where(valid[:, None], (c2w * grad_c[:, None, :]).sum(-1), dflt_g[None])
-    else:
-        feat, sdf, sdf_grad, c2w = _SelectPush.apply(out, grad_c, valid, d["fwd_J"] if win is not None else None,
-                                                     d["cand_src"], d["sel"])
+    else:                                      # one kernel each way (ia_select_push / _bwd)
+        feat, sdf, sdf_grad, c2w = _SelectPush.apply(out, grad_c, valid, d["fwd_J"] if found else None, d["cand_src"], d["sel"])
     w2s_rot = dfm.w2s[:3, :3].contiguous()
     normal_smpl, normal_world, refl01 = _ShadePrep.apply(sdf_grad, rays_d, ray_indices, w2s_rot)
     alphas = _Alpha.apply(sdf, t_ends - t_starts, rs.density.get_beta())
-    rgbs = _Radiance.apply(pts_cano, rad.grid_params, feat, refl01, normal_world, *rad.effective_weights(),
+    return ShadeFront(d, pts_cano, feat, sdf, sdf_grad, c2w, grad_c, valid, normal_smpl, normal_world, refl01, alphas, w2s_rot, geo_w, J_inv_win)
+
+
+def shade_differentiable(rs, rays_o: Tensor, rays_d: Tensor, ray_indices: Tensor, t_starts: Tensor, t_ends: Tensor,
+                         packed_info: Tensor, curv_u: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """differentiable rgb_normal_alpha_fn + rendering_with_normals_sdf for the samples found by the no-grad pass.
+    curv_u [n_samples,3]: uniforms for the curvature probe directions (enables out["sdf_laplace"])."""
+    geo, rad = rs.geometry, rs.radiance
+    f = shade_front(rs, rays_o, rays_d, ray_indices, t_starts, t_ends, geo.prog.level_bits,
+                    rs.deformer.tfs.requires_grad and torch.is_grad_enabled())
+    rgbs = _Radiance.apply(f.pts_cano, rad.grid_params, f.feat, f.refl01, f.normal_world, *rad.effective_weights(),
                            rad.center, rad.scale, rad.prog.level_bits())
-    weights, trans = nerfacc._WeightFromAlpha.apply(alphas, packed_info)
+    weights, trans = nerfacc._WeightFromAlpha.apply(f.alphas, packed_info)
     acc = lambda v: nerfacc._Accumulate.apply(weights, v, ray_indices, packed_info)      # noqa: E731
-    res = dict(comp_rgb=acc(rgbs), comp_normal=acc(normal_world), opacity=acc(None),
-               depth=acc(((t_starts + t_ends) / 2.0)[:, None]), weights=weights, alphas=alphas, rgbs=rgbs, sdf=sdf,
-               sdf_grad=sdf_grad, valid=valid, n_samples=pts.shape[0], pts_cano=d["pts_cano"], c2w=c2w)
-    if pose_grad and win is not None:
-        res["J_inv"] = J_inv_win
+    res = dict(comp_rgb=acc(rgbs), comp_normal=acc(f.normal_world), opacity=acc(None),
+               depth=acc(((t_starts + t_ends) / 2.0)[:, None]), weights=weights, alphas=f.alphas, rgbs=rgbs, sdf=f.sdf,
+               sdf_grad=f.sdf_grad, valid=f.valid, n_samples=t_starts.shape[0], pts_cano=f.d["pts_cano"], c2w=f.c2w)
+    if f.J_inv_win is not None:
+        res["J_inv"] = f.J_inv_win
     if curv_u is not None:       # laplace = 0 for points without a valid candidate (snarf_deformer.py:233-235)
-        res["sdf_laplace"] = curvature_laplace(geo, d["pts_cano"], grad_c, curv_u) * valid.float()
+        res["sdf_laplace"] = curvature_laplace(geo, f.d["pts_cano"], f.grad_c, curv_u) * f.valid.float()
     return res
 
 

@@ -20,7 +20,7 @@ from torch import Tensor
 from torch.autograd import Function
 
 from . import _lib as L
-from . import fields, lib_nerfacc, nerfacc, pbr, render, train
+from . import fields, lib_nerfacc, nerfacc, pbr, train
 from .tinycudann import _SH4
 
 
@@ -157,41 +157,31 @@ def shade_differentiable_phys(rs, material, emitter, rays_o: Tensor, rays_d: Ten
     along the camera ray -- from env_base when given, else the emitter's image -- and the emitter receives their gradient.
     curv_u [n_samples,3]: uniforms for the curvature probe directions (model.with_curvature_loss): enables res["sdf_laplace"], as
     train.shade_differentiable does."""
-    dfm, geo, rad = rs.deformer, rs.geometry, rs.radiance
+    geo, rad = rs.geometry, rs.radiance
     n_rays = packed_info.shape[0]
     dev = rays_o.device
-    pts = render.ray_points(rays_o, rays_d, ray_indices, t_starts, t_ends)
-    with torch.no_grad():
-        d = dfm.deform(pts, geo, with_grad=False, with_feature=False, want_fwd=True)
-        valid = d["valid"]
-    W1k, b1, W2, b2 = geo.effective_weights()
-    out, grad_c = train._SDFField.apply(d["pts_cano"], geo.grid_params, W1k, b1, W2, b2, geo.center, geo.scale, 0xFFFFFFFF,
-                                            geo.inv_scale_host())
-    # invalid points: sdf 1e5, feature 0, gradient [0,0,1] (snarf_deformer.py:192-231); valid ones: the normal push-forward with the
-    # winning candidate's blended rotation -- one kernel each way (ia_select_push / _bwd)
-    feat, sdf, sdf_grad, _c2w = train._SelectPush.apply(out, grad_c, valid, d["fwd_J"] if d["n_candidates"] > 0 else None, d["cand_src"], d["sel"])
-    w2s_rot = dfm.w2s[:3, :3].contiguous()
-    normal_smpl, normal_world, refl01 = train._ShadePrep.apply(sdf_grad, rays_d, ray_indices, w2s_rot)
-    alphas = train._Alpha.apply(sdf, t_ends - t_starts, rs.density.get_beta())
+    # every hash level takes a gradient, no pose terms (train.shade_differentiable: the active levels, pose terms)
+    f = train.shade_front(rs, rays_o, rays_d, ray_indices, t_starts, t_ends, lambda: 0xFFFFFFFF, False)
+    n_samples = t_starts.shape[0]
     # hash grid #2 once; radiance and material heads
     with torch.no_grad():
-        xp2 = fields.normalize_points(d["pts_cano"], rad.center, rad.scale)
+        xp2 = fields.normalize_points(f.d["pts_cano"], rad.center, rad.scale)
     enc2 = _HashEncode.apply(xp2, rad.grid_params)
-    sh = _SH4.apply(refl01)
-    rgbs = _MLP2.apply(1, 3, *rad.effective_weights(), enc2, xp2, feat, sh, normal_world)
+    sh = _SH4.apply(f.refl01)
+    rgbs = _MLP2.apply(1, 3, *rad.effective_weights(), enc2, xp2, f.feat, sh, f.normal_world)
     mask = rad.prog.mask(rad.global_step, dev)
     mat_w = material.effective_weights(mask)             # once per step: the jitter pass reads the same matrices
-    mraw = _MLP2.apply(2, 5, *mat_w, enc2, xp2, feat)
+    mraw = _MLP2.apply(2, 5, *mat_w, enc2, xp2, f.feat)
     albedo, rough, metal = _MaterialAffine.apply(mraw, material)
-    weights, trans = nerfacc._WeightFromAlpha.apply(alphas, packed_info)
+    weights, trans = nerfacc._WeightFromAlpha.apply(f.alphas, packed_info)
     acc = lambda v: nerfacc._Accumulate.apply(weights, v, ray_indices, packed_info)      # noqa: E731
     extra_maps = {}
     if jitter_n is not None:
         # material jitter pass: geometry feature + radiance embedding + material head at the jittered canonical points
         # (material_feature = hybrid); no deformer, no validity mask, exactly as the reference evaluates it
         with torch.no_grad():
-            x_j = (d["pts_cano"] + 0.01 * jitter_n[:pts.shape[0]]).contiguous()
-        out_j, _ = train._SDFField.apply(x_j, geo.grid_params, W1k, b1, W2, b2, geo.center, geo.scale, 0xFFFFFFFF, geo.inv_scale_host())
+            x_j = (f.d["pts_cano"] + 0.01 * jitter_n[:n_samples]).contiguous()
+        out_j, _ = train._SDFField.apply(x_j, geo.grid_params, *f.geo_w, geo.center, geo.scale, 0xFFFFFFFF, geo.inv_scale_host())
         xp2_j = fields.normalize_points(x_j, rad.center, rad.scale)
         enc2_j = _HashEncode.apply(xp2_j, rad.grid_params)
         mraw_j = _MLP2.apply(2, 5, *mat_w, enc2_j, xp2_j, out_j)
@@ -200,54 +190,41 @@ def shade_differentiable_phys(rs, material, emitter, rays_o: Tensor, rays_d: Ten
         def rel(v, vj):            # compute_relative_smoothness_loss (:383-388)
             base = torch.maximum(v, vj).clamp_min(1e-6)
             return (((v - vj) / base) ** 2).sum(-1, keepdim=True)
-        orient = (rays_d[ray_indices] * normal_smpl).sum(-1, keepdim=True).clamp_min(0.0)
+        orient = (rays_d[ray_indices] * f.normal_smpl).sum(-1, keepdim=True).clamp_min(0.0)
         extra_maps = dict(normals_orientation_loss_map=acc(orient.contiguous()),
                           albedo_smoothness_loss_map=acc(rel(albedo, alb_j).contiguous()),
                           roughness_smoothness_loss_map=acc(rel(rough, rough_j).contiguous()),
                           metallic_smoothness_loss_map=acc(rel(metal, metal_j).contiguous()))
-    res = dict(comp_rgb=acc(rgbs), comp_normal=acc(normal_world), opacity=acc(None), albedo=acc(albedo),
-               roughness=acc(rough), metallic=acc(metal), weights=weights, alphas=alphas, sdf=sdf,
-               sdf_grad=sdf_grad, valid=valid, n_samples=pts.shape[0], **extra_maps)
+    res = dict(comp_rgb=acc(rgbs), comp_normal=acc(f.normal_world), opacity=acc(None), albedo=acc(albedo),
+               roughness=acc(rough), metallic=acc(metal), weights=weights, alphas=f.alphas, sdf=f.sdf,
+               sdf_grad=f.sdf_grad, valid=f.valid, n_samples=n_samples, **extra_maps)
     if curv_u is not None:       # laplace = 0 for points without a valid candidate (snarf_deformer.py:233-235)
-        res["sdf_laplace"] = train.curvature_laplace(geo, d["pts_cano"], grad_c, curv_u[:pts.shape[0]]) * valid.float()
+        res["sdf_laplace"] = train.curvature_laplace(geo, f.d["pts_cano"], f.grad_c, curv_u[:n_samples]) * f.valid.float()
     # ---- volume scattering (enable_phys)
     if background_color is None:
         background_color = torch.ones(3, device=dev)
     rgb_phys = background_color[None].expand(n_rays, 3)
     bg_rays = None
     if add_emitter:
-        rgb_phys = bg_rays = emitter.background(rays_d, w2s_rot, env_base=env_base)
+        rgb_phys = bg_rays = emitter.background(rays_d, f.w2s_rot, env_base=env_base)
         res["background_rays"] = bg_rays
     stats = dict(n_resampled=0, n_fg=0, n_secondary=0)
     if ray_indices.numel() > 0:
-        vi = pbr.VolumeInteraction(ray_indices, t_starts, t_ends, n_rays, spp, weights, sdf)
+        vi = pbr.VolumeInteraction(ray_indices, t_starts, t_ends, n_rays, spp, weights, f.sdf)
         stats["n_resampled"], stats["n_fg"] = vi.R, vi.F
         if vi.F > 0:
             F_ = vi.F
             # differentiable gathers of the per-interval attributes + re-sampled weights w[s] / count[s] (ia_vi_gather / _bwd)
-            w_fg, nrm, alb, rgh, mtl = vi.gather(rays_o, rays_d, weights, normal_smpl, albedo, rough, metal)
+            w_fg, nrm, alb, rgh, mtl = vi.gather(rays_o, rays_d, weights, f.normal_smpl, albedo, rough, metal)
             with torch.no_grad():
-                inv_pdf = None
-                if render_mode == "light" and light_sampling == "per_point":
-                    u = light_u[:F_].contiguous() if light_u is not None else None
-                    dirs = emitter.sample(F_, u, w2s_rot=w2s_rot)                      # emitter.sample + transform_dirs_w2s
-                    ro, rd, src, out_dirs = pbr.secondary_rays(nrm, vi.positions, dirs)
-                else:
-                    if render_mode == "light":
-                        dirs_smpl = emitter.sample(spp, light_u, w2s_rot=w2s_rot)
-                        inv_pdf_all = None
-                    else:
-                        assert spp == 512, "uniform_light asserts samples_per_pixel == 512 (:1392)"
-                        dirs_smpl, inv_pdf_all = pbr.uniform_sphere_stratified(16, 32, light_u[:, :2])
-                    shuffled = vi.shuffle(shuffle_u)
-                    ro, rd, src, out_dirs = pbr.secondary_rays(nrm, vi.positions, dirs_smpl, dir_index=shuffled)
-                    inv_pdf = inv_pdf_all[shuffled.long()] if inv_pdf_all is not None else None
+                ro, rd, src, out_dirs, inv_pdf, _ = pbr.light_rays(vi, nrm, emitter, f.w2s_rot, render_mode, spp, light_u, shuffle_u,
+                                                                   light_sampling)
                 stats["n_secondary"] = int(ro.shape[0])
                 t_, c_ = rs.compute_indirect_radiance(ro, rd)
                 sec_tr, sec_rgb = pbr.scatter_secondary(F_, src, t_, c_)
             fg_Lo, fg_Ld, fg_Ls = pbr.pbr_shade_differentiable(
                 render_mode, nrm, alb, rgh, mtl, vi.view_dirs, out_dirs, sec_tr, sec_rgb if global_illumination else None, emitter,
-                w2s_rot, inv_pdf=inv_pdf, env_base=env_base)
+                f.w2s_rot, inv_pdf=inv_pdf, env_base=env_base)
             # background re-samples carry the background colour (Lo.scatter_(0, bg_indices, background_color), :1335-1342),
             # their weights sum to the ray's transmittance; rays without samples show the background (:1452-1466)
             rgb_phys = vi.composite(w_fg, fg_Lo, 1.0 - res["opacity"], background_color, bg_rays)
