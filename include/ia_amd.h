@@ -991,6 +991,24 @@ int ia_mesh_vertex_faces_fill(int64_t T, int64_t V, const int64_t* faces, const 
 int ia_mesh_vertex_normals(int64_t V, int64_t T, const float* v_pos, const int64_t* faces, const int32_t* offsets, int32_t* lists,
                            float* v_nrm, ia_stream_t stream);
 
+/* ------------------------------------------------------------------------- */
+/* Pose terms, backward (csrc/pose_terms.hip): the gradient of the bone transforms through the implicit-function correction of the
+ * canonical roots (ForwardDeformer.forward version 1, deformer_torch.py:57-76) and the blended rotation of the normal push-forward
+ * (snarf_deformer.py:176-184), for the winning roots.  The forward pass needs no kernel: both terms are zero in value.
+ *
+ * ia_pose_terms_bwd: xc [P,3], valid [P] (bytes, non-zero = valid), g_pts [P,3] = d loss / d pts_cano, g_c2w [P,3,3] = d loss / d c2w,
+ *   J_inv [n_jinv,3,3] with win [P] int64 = the row of point p (win NULL: row p, n_jinv >= P; a row index outside [0, n_jinv) makes the
+ *   point contribute nothing), the weight grid with offset / scale as ia_forward_skinning takes them (all fp32, on the device) ->
+ *   g_tfs [24,4,4]:  w_p = the weights of ia_forward_skinning at xc_p (the same bits), gx_p = -J_inv_p^T g_pts_p,
+ *   G_p [3,4] = [ g_c2w_p + gx_p xc_p^T | gx_p ], g_tfs[j][:3,:4] = sum over the valid p of w_p[j] G_p, g_tfs[j][3,:] = 0.  An invalid
+ *   point is not read beyond its flag.  G and the sums are formed in fp64 in a fixed order (per-block partial sums, added in a fixed
+ *   order of the blocks, one rounding to fp32): no atomics, bit-identical from call to call.  P = 0 writes zeros.
+ *   tmp: ia_pose_terms_bwd_tmp_size(P) bytes, 8-byte aligned (may be NULL when P = 0); consumed by the call. */
+int64_t ia_pose_terms_bwd_tmp_size(int64_t P);
+int ia_pose_terms_bwd(int64_t P, const float* xc, const float* J_inv, const int64_t* win, int64_t n_jinv, const uint8_t* valid,
+                      const float* g_pts, const float* g_c2w, const float* grid, int D, int H, int W, const float* offset,
+                      const float* scale, float* g_tfs, void* tmp, ia_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ SOURCES = {
     "mesh_attr.hip": ["-ffp-contract=off"],
     "train_loss.hip": ["-ffp-contract=off"],
     "lpips.hip": ["-ffp-contract=off"],
+    "pose_terms.hip": ["-ffp-contract=off"],
 }
 
 

@@ -21,6 +21,28 @@ from . import _lib as L
 from . import fast_snarf
 
 
+class _PoseTerms(torch.autograd.Function):
+    """SNARFDeformer.implicit_pose_terms + `c2w + (R - R.detach()) * valid` as one node.  Both terms are zero in value, so forward
+    hands back xc and c2w as they came (views: no launch, nothing reads tfs); backward is ia_pose_terms_bwd, once, and yields the
+    gradient of tfs [B,24,4,4] (pose 0, as implicit_pose_terms reads it).  xc / c2w pass their gradients through unchanged."""
+
+    @staticmethod
+    def forward(ctx, tfs, xc, c2w, J_inv, valid, win, dfm):
+        ctx.save_for_backward(xc, J_inv, valid, win)
+        ctx.dfm, ctx.tfs_shape = dfm, tuple(tfs.shape)
+        return xc.view_as(xc), c2w.view_as(c2w)
+
+    @staticmethod
+    def backward(ctx, g_pts, g_c2w):
+        xc, J_inv, valid, win = ctx.saved_tensors
+        g_tfs = None
+        if ctx.needs_input_grad[0]:
+            g = ctx.dfm.pose_terms_backward(xc, J_inv, valid, g_pts, g_c2w, win)
+            B = ctx.tfs_shape[0]
+            g_tfs = g[None] if B == 1 else torch.cat([g[None], L.zeros((B - 1, 24, 4, 4), g.device)], 0)
+        return (g_tfs, g_pts if ctx.needs_input_grad[1] else None, g_c2w if ctx.needs_input_grad[2] else None, None, None, None, None)
+
+
 class SNARFDeformer:
     INIT_BONES = [0, 1, 2, 4, 5, 10, 11, 12, 15, 16, 17, 18, 19]    # deformer_torch.py:27
     # K9-consistent early filter of the search (fast_snarf.fuse_broyden_spec[_rows], csrc/snarf.hip, DESIGN 4.5): a search is retired
@@ -208,6 +230,31 @@ class SNARFDeformer:
         corr = -(J_inv * (xd - xd.detach())[:, None, :]).sum(-1)
         corr = corr * valid[:, None].to(corr.dtype)
         return xc + corr, R
+
+    def pose_terms(self, xc: Tensor, c2w: Tensor, J_inv: Tensor, valid: Tensor, win: Optional[Tensor] = None):
+        """implicit_pose_terms as one autograd node (_PoseTerms): -> (pts_cano, c2w) with the VALUES of xc and c2w and the derivative
+        with respect to self.tfs of `xc + correction` and `c2w + (R - stopgrad(R)) * valid`.  Forward launches nothing; backward is one
+        fused kernel (ia_pose_terms_bwd: weight lookup, J_inv gather and the [24 x P] . [P x 12] reduction in one pass, no library
+        product, no per-sample intermediate).  J_inv [P,3,3], or with win [P] (int64) any [N,3,3] list that win indexes."""
+        return _PoseTerms.apply(self.tfs, xc, c2w, J_inv, valid, win, self)
+
+    def pose_terms_backward(self, xc: Tensor, J_inv: Tensor, valid: Tensor, g_pts: Tensor, g_c2w: Tensor,
+                            win: Optional[Tensor] = None) -> Tensor:
+        """ia_pose_terms_bwd on this deformer's weight grid -> g_tfs [24,4,4] (row 3 of every matrix is 0)."""
+        if not xc.is_cuda:
+            raise L.IaError("SNARFDeformer.pose_terms_backward needs GPU tensors (no CPU fallback)")
+        P = int(xc.shape[0])
+        _, _, D, H, W = self.lbs_voxel_final.shape
+        c = lambda t: t.detach().contiguous().float()      # noqa: E731
+        J_inv = c(J_inv).reshape(-1, 3, 3)
+        g_tfs = torch.empty((24, 4, 4), device=xc.device)
+        nb = int(L.lib().ia_pose_terms_bwd_tmp_size(P))
+        L.lib().ia_pose_terms_bwd(P, c(xc), J_inv, win.contiguous().long() if win is not None else None, int(J_inv.shape[0]),
+                                  valid.detach().contiguous() if valid.dtype in (torch.bool, torch.uint8) else (valid != 0).contiguous(),
+                                  c(g_pts), c(g_c2w).reshape(-1, 3, 3),
+                                  self.lbs_voxel_final, D, H, W, self.offset_kernel, self.scale_kernel, g_tfs,
+                                  L.work_area(nb, xc.device) if nb else None)
+        return g_tfs
 
     @torch.no_grad()
     def _pack_candidates(self, x: Tensor, valid: Tensor, with_src: bool):

@@ -6,6 +6,14 @@ IntrinsicAvatarModel.update_step (models/intrinsic_avatar.py:224-275), Intrinsic
     FitConfig    the `model`, `system.loss`, `trainer` (and the scalar `system` / optimiser) values of configs/config.yaml
     Trainer      one frame per step: batch -> pose -> grid -> forward -> fused loss -> backward -> Adam -> LR schedule
 
+Pose correction (Trainer(..., pose_correction=pose_correction.PoseCorrection(...)), config.enable_pose_correction): order within a
+step as in systems/base.py:109-111 -- the frame is posed with the module's switch as the PREVIOUS step left it, only then does
+update_step(epoch, global_step) run.  update_step turns the switch on when global_step > pose_correction_start_step = S, i.e. during
+step S + 1, after that step's pose: the first step that adds corrections has global_step = S + 2.  From then on the step's
+body_pose / global_orient / transl are the dataset's plus the frame's rows, SMPL kinematics run with grad, the deformer is prepared
+with the differentiable tfs and the DETACHED w2s (snarf_deformer.py:130,148,156), and the grid update and reinit_grids pose every
+frame with its corrected parameters under no_grad.  betas_correction is carried in the state dict and never added (optimize_betas: false).
+
 Random numbers: EVERY random tensor of a step comes from the Trainer's one generator, drawn at the top of step() in this order
 (a tensor that the step's phase does not use is not drawn), and is returned in the step's record so that the step can be replayed:
 
@@ -85,17 +93,19 @@ class FitConfig:
     scene_aabb: List[float] = field(default_factory=lambda: [-1.25, -1.55, -1.25, 1.25, 0.95, 1.25])
     cano_pose: object = "da_pose"
     enable_pose_correction: bool = False
+    pose_correction_start_step: int = 4000
+    pose_correction_wd: float = 1e-5
     optimize_betas: bool = False
     reinit_optimizer_steps: List[int] = field(default_factory=list)
     world_size: int = 1
 
-    def check_scope(self) -> None:
-        """raises NotImplementedError for what this driver does not do"""
+    def check_scope(self, pose_correction=None) -> None:
+        """raises NotImplementedError for what this driver does not do; pose_correction: the module the Trainer was given"""
         def positive(v):
             return any(float(x) > 0 for x in (v[-3:-1] if isinstance(v, (list, tuple)) else [v or 0.0]))
         bad = []
-        if self.enable_pose_correction:
-            bad.append("enable_pose_correction: the pose-correction module is outside the render-step path")
+        if self.enable_pose_correction and pose_correction is None:
+            bad.append("enable_pose_correction: needs a module (Trainer(..., pose_correction=pose_correction.PoseCorrection(...)))")
         if self.optimize_betas:
             bad.append("optimize_betas: SMPL shape optimisation is outside the render-step path")
         if int(self.system.get("reinit_shape_every_n_steps", -1) or -1) > 0:
@@ -183,21 +193,29 @@ _SAMPLE_SLACK = 40          # samples per ray beyond num_samples_per_ray that th
 class Trainer:
     """rs: render.RenderStep (geometry, radiance, density, deformer); material: fields.VolumeMaterial; emitter: a pbr.EnvironmentLight*;
     frames: data.TrainingFrames / TruthFrames with a sampler; body: smpl.SMPLKinematics; generator: the one source of random numbers
-    (of the frames' device, or of the CPU: then every draw is made on the host and copied)."""
+    (of the frames' device, or of the CPU: then every draw is made on the host and copied); pose_correction: a
+    pose_correction.PoseCorrection with one row per frame (moved to the frames' device), or None: the dataset's SMPL fits as they are.
+    The module's own enable flag and start step are the ones it was built with; the config's say whether a module is expected."""
 
-    def __init__(self, rs, material, emitter, frames, body, config: Optional[FitConfig] = None, generator: Optional[torch.Generator] = None):
+    def __init__(self, rs, material, emitter, frames, body, config: Optional[FitConfig] = None, generator: Optional[torch.Generator] = None,
+                 pose_correction=None):
         self.config = config if config is not None else FitConfig()
-        self.config.check_scope()
+        self.config.check_scope(pose_correction)
         if frames.sampler is None:
             raise ValueError("fit.Trainer needs frames with a pixel sampler")
         self.rs, self.material, self.emitter, self.frames, self.body = rs, material, emitter, frames, body
         self.device = frames.device
+        self.pose_correction = pose_correction.to(self.device) if pose_correction is not None else None
+        if self.pose_correction is not None and self.pose_correction.dataset_length != len(frames):
+            raise ValueError(f"pose_correction has {self.pose_correction.dataset_length} rows for {len(frames)} frames")
         self.generator = generator if generator is not None else torch.Generator(device=self.device)
         self.schedule = Schedule(self.config)
         oc, sc = self.config.optimizer, self.config.system
         self.optimizer, self.scheduler = optim.reference_optimizer(rs, lr=oc["lr"], color_grid_wd=oc["color_grid_wd"], material=material,
                                                                    emitter=emitter, warmup_steps=sc["warmup_steps"],
-                                                                   milestones=tuple(oc["milestones"]), gamma=oc["gamma"])
+                                                                   milestones=tuple(oc["milestones"]), gamma=oc["gamma"],
+                                                                   pose_correction=self.pose_correction,
+                                                                   pose_correction_wd=float(self.config.pose_correction_wd))
         for g in self.optimizer.param_groups:
             g["betas"], g["eps"] = tuple(oc["betas"]), oc["eps"]
         self.grid = self._new_grid(torch.tensor(self.config.scene_aabb, dtype=torch.float32).reshape(1, 6), 1)
@@ -229,19 +247,35 @@ class Trainer:
         grid.train()
         return grid
 
-    @torch.no_grad()
     def pose(self, params: Dict[str, Tensor]) -> Tensor:
         """animation.prepare_frame without its occupancy grid: SMPL kinematics -> deformer.prepare -> canonical bbox to both fields.
-        -> the box of the posed vertices in SMPL space [6] (get_bbox_from_smpl)."""
+        -> the box of the posed vertices in SMPL space [6] (get_bbox_from_smpl).  Parameters that carry a graph (corrected_params
+        with the switch on, grad mode on) leave a deformer whose tfs requires grad; w2s is detached either way."""
         rs, body, dfm = self.rs, self.body, self.rs.deformer
         dt = body.v_template.dtype
-        out = body.forward(params["betas"].to(dt), params["body_pose"].to(dt), params["global_orient"].to(dt), params["transl"].to(dt))
-        tfs, w2s = smpl.deformer_transforms(out["A"], self.A_rest_inv)
+        with torch.set_grad_enabled(torch.is_grad_enabled() and any(v.requires_grad for v in params.values())):
+            out = body.forward(params["betas"].to(dt), params["body_pose"].to(dt), params["global_orient"].to(dt), params["transl"].to(dt))
+            tfs, w2s = smpl.deformer_transforms(out["A"], self.A_rest_inv)
+        w2s = w2s.detach()
         dfm.prepare(tfs, w2s[0])
-        rs.geometry.prepare_bbox(dfm.bbox)
-        rs.radiance.prepare_bbox(dfm.bbox)
-        verts = out["vertices"].float() @ w2s[:, :3, :3].permute(0, 2, 1) + w2s[:, None, :3, 3]
-        return smpl.bbox_from_vertices(verts).reshape(-1).to(self.device)
+        with torch.no_grad():
+            rs.geometry.prepare_bbox(dfm.bbox)
+            rs.radiance.prepare_bbox(dfm.bbox)
+            verts = out["vertices"].float() @ w2s[:, :3, :3].permute(0, 2, 1) + w2s[:, None, :3, 3]
+            return smpl.bbox_from_vertices(verts).reshape(-1).to(self.device)
+
+    def corrected_params(self, idx: int, params: Optional[Dict[str, Tensor]] = None) -> Dict[str, Tensor]:
+        """frame idx's SMPL parameters (`params`, or the dataset's) plus the module's rows: body_pose, global_orient and transl;
+        betas stay the dataset's.  Without a module, or while its switch is off, `params` as they are (nothing is added, not even
+        zeros: the step is bit-identical to one without the module)."""
+        params = params if params is not None else self._frame_params(idx)
+        pc = self.pose_correction
+        if pc is None or not pc.enable_pose_correction:
+            return params
+        c = pc(torch.tensor([idx], dtype=torch.int64, device=self.device))
+        return dict(betas=params["betas"], body_pose=params["body_pose"] + c["pose_correction"].to(params["body_pose"].dtype),
+                    global_orient=params["global_orient"] + c["global_orient_correction"].to(params["global_orient"].dtype),
+                    transl=params["transl"] + c["transl_correction"].to(params["transl"].dtype))
 
     def occ_eval_fn(self) -> Callable:
         """alpha of one render step at posed-space points: the occ_eval_fn of animation.prepare_frame"""
@@ -267,7 +301,7 @@ class Trainer:
             rand = self._draw("uniform", F, res ** 3, 3, 3)
         occs, binaries, aabbs = [], [], []
         for idx in range(F):
-            aabb = self.pose(self._frame_params(idx))
+            aabb = self.pose(self.corrected_params(idx))
             o, b = occ_grid.compute_test_occupancy_grid(self.occ_eval_fn(), aabb, res, 3, float(self.config.model["grid_prune_occ_thre"]), rand[idx])
             occs.append(o)
             binaries.append(b)
@@ -348,7 +382,7 @@ class Trainer:
 
     def step(self) -> Dict:
         """one optimisation step; -> the step's record: `phase`, `frame`, `random` (the tensors drawn), `lr` (per parameter group, as
-        used by this step), `loss`, `terms`, `num_samples`, `grid_level`, `grid_levels`, `out` (the model's output dict)."""
+        used by this step), `pose_correction_enabled` (the frame was posed with its corrections), `loss`, `terms`, `num_samples`, `grid_level`, `grid_levels`, `out` (the model's output dict)."""
         cfg, frames, rs, F = self.config, self.frames, self.rs, len(self.frames)
         new_epoch = self._perm is None or self._pos >= F
         if new_epoch and self._perm is not None:
@@ -366,17 +400,22 @@ class Trainer:
         batch, background, _ = system.preprocess_data(batch, "train", background_color=bg_mode if bg_mode != "random" else "white",
                                                       background=r.get("background"))
         t_idx = idx / F                                        # the batch's t_idx, on the host
-        # 4. pose
-        params = {k: batch[k] for k in ("betas", "body_pose", "global_orient", "transl")}
+        # 4. pose: with the corrections of the frame's rows once the module's switch is on -- as the PREVIOUS step left it
+        # (systems/base.py:109-111: the batch is preprocessed, i.e. posed, before update_step); tfs then carries the graph to them
+        pc = self.pose_correction
+        pc_on = pc is not None and pc.enable_pose_correction
+        self.optimizer.zero_grad(set_to_none=True)
+        params = self.corrected_params(idx, {k: batch[k] for k in ("betas", "body_pose", "global_orient", "transl")})
         self.pose(params)
-        # 5. the modules' step counters (progressive hash levels, SH annealing)
-        for mod in (rs.geometry, rs.radiance, rs.density):
-            if hasattr(mod, "update_step"):
+        # 5. the modules' step counters (progressive hash levels, SH annealing, the pose-correction switch)
+        for mod in (rs.geometry, rs.radiance, rs.density, pc):
+            if mod is not None and hasattr(mod, "update_step"):
                 mod.update_step(self.epoch, self.global_step)
         # 6. occupancy grid: EMA update of the frame's level, then (at its steps) one grid per frame
         if ph.grid_update:
-            self.grid.update_every_n_steps(self.global_step, t_idx, self.occ_eval_fn(), occ_thre=float(cfg.model["grid_prune_occ_thre"]),
-                                           ema_decay=float(cfg.model["grid_prune_ema_decay"]), n=int(cfg.grid_update_every), rand=r["grid_rand"])
+            with torch.no_grad():
+                self.grid.update_every_n_steps(self.global_step, t_idx, self.occ_eval_fn(), occ_thre=float(cfg.model["grid_prune_occ_thre"]),
+                                               ema_decay=float(cfg.model["grid_prune_ema_decay"]), n=int(cfg.grid_update_every), rand=r["grid_rand"])
         if ph.reinit_grid:
             self.reinit_grids(r["reinit_rand"])
             self.pose(params)
@@ -384,7 +423,6 @@ class Trainer:
         lvl = self._point_at_level(t_idx)
         rs.importance_sample = ph.importance_sample
         # 9. - 11.
-        self.optimizer.zero_grad(set_to_none=True)
         out = self.forward(ph, batch["rays"], background, r)
         n_samples = int(out["sdf_samples"].shape[0])
         if n_samples > self.sample_cap:
@@ -400,7 +438,7 @@ class Trainer:
             self.scheduler.step()
         rec = dict(global_step=self.global_step, epoch=self.epoch, phase=ph, frame=idx, random=r, lr=lr, loss=loss.detach(),
                    terms={k: v.detach() for k, v in terms.items()}, num_samples=out["num_samples"], grid_level=lvl,
-                   grid_levels=int(self.grid.levels), background=background, batch=batch, out=out)
+                   grid_levels=int(self.grid.levels), background=background, batch=batch, out=out, pose_correction_enabled=bool(pc_on))
         self.global_step += 1
         return rec
 
@@ -423,6 +461,9 @@ class Trainer:
         sd = dict(checkpoint.reference_state_dict(self.rs, self.material))
         sd.update({"model.occupancy_grid." + k: v for k, v in self.grid.state_dict().items()})
         sd.update({"model.emitter." + k: v for k, v in self.emitter.state_dict().items()})
+        if self.pose_correction is not None:
+            sd.update({"model.pose_correction." + k: v for k, v in self.pose_correction.state_dict().items()})
+            sd["pose_correction_enabled"] = bool(self.pose_correction.enable_pose_correction)
         sd["optimizer"] = self.optimizer.state_dict()
         sd["scheduler"] = self.scheduler.state_dict() if self.scheduler is not None else None
         sd["global_step"], sd["epoch"] = self.global_step, self.epoch
@@ -438,6 +479,10 @@ class Trainer:
         self.grid = self._new_grid(grid["aabbs"].cpu(), int(grid["binaries"].shape[0]))
         self.grid.load_state_dict(grid, strict=True)
         self.emitter.load_state_dict({k[len("model.emitter."):]: v for k, v in model.items() if k.startswith("model.emitter.")}, strict=True)
+        if self.pose_correction is not None:
+            self.pose_correction.load_state_dict({k[len("model.pose_correction."):]: v for k, v in model.items()
+                                                  if k.startswith("model.pose_correction.")}, strict=True)
+            self.pose_correction.enable_pose_correction = bool(sd.get("pose_correction_enabled", False))
         fields.params_changed()
         self.optimizer.load_state_dict(copy.deepcopy(sd["optimizer"]))
         if self.scheduler is not None and sd.get("scheduler") is not None:

@@ -98,10 +98,12 @@ class Adam(torch.optim.Optimizer):
         return loss
 
 
-def reference_param_groups(rs, lr: float = 1e-3, color_grid_wd: float = 0.0, material=None, emitter=None):
+def reference_param_groups(rs, lr: float = 1e-3, color_grid_wd: float = 0.0, material=None, emitter=None, pose_correction=None,
+                           pose_correction_wd: float = 1e-5):
     """the parameter groups of configs/config.yaml:116-136 for a RenderStep (names as in the reference config):
     geometry (hash grid + SDF head), radiance.network, radiance.xyz_encoding (with `color_grid_wd` L2 decay), density
-    (lr 1e-3), and, for the PBR branch, material / emitter."""
+    (lr 1e-3), for the PBR branch material / emitter, and, with a pose_correction.PoseCorrection module, pose_correction (lr 1e-4,
+    `pose_correction_wd` L2 decay, :117-119; dense: every row of the embeddings decays, as torch.optim.Adam treats an nn.Embedding)."""
     geo, rad = rs.geometry, rs.radiance
     rad_grid = [rad.grid_params]
     rad_net = [p for p in rad.parameters() if p is not rad.grid_params and p.requires_grad]
@@ -113,22 +115,25 @@ def reference_param_groups(rs, lr: float = 1e-3, color_grid_wd: float = 0.0, mat
         groups.append(dict(params=list(material.parameters()), name="material", lr=lr))
     if emitter is not None:
         groups.append(dict(params=list(emitter.parameters()), name="emitter", lr=lr))
+    if pose_correction is not None:
+        groups.append(dict(params=list(pose_correction.parameters()), name="pose_correction", lr=1e-4, weight_decay=pose_correction_wd))
     return [g for g in groups if g["params"]]
 
 
 def reference_optimizer(rs, lr: float = 1e-3, color_grid_wd: float = 0.0, material=None, emitter=None,
                         grad_scale: float = 1.0, warmup_steps: Optional[int] = 1000,
-                        milestones=(12500, 18750, 22500, 23750), gamma: float = 0.3):
+                        milestones=(12500, 18750, 22500, 23750), gamma: float = 0.3, pose_correction=None,
+                        pose_correction_wd: float = 1e-5):
     """Adam + the scheduler of configs/config.yaml:137-155: SequentialLR(LinearLR 0.01 -> 1 over `warmup_steps`,
     then MultiStepLR(milestones, gamma) -- milestones count from the END of the warm-up, as SequentialLR restarts the
     second scheduler's step counter).  returns (optimizer, scheduler or None).
 
     The parameter groups are the reference's for the modules a RenderStep owns (geometry, radiance.network,
-    radiance.xyz_encoding, density, material, emitter); the reference's pose_correction / pose_encoder / deformer groups
-    belong to modules outside the render_step path, so an optimiser checkpoint of the full reference model does NOT load
-    here -- only same-group torch.optim.Adam state does."""
-    opt = Adam(reference_param_groups(rs, lr, color_grid_wd, material, emitter), lr=lr, betas=(0.9, 0.99), eps=1e-15,
-               grad_scale=grad_scale)
+    radiance.xyz_encoding, density, material, emitter) and, when a pose_correction.PoseCorrection module is given, its
+    pose_correction group; the reference's pose_encoder / deformer groups belong to modules outside the render_step path, so an
+    optimiser checkpoint of the full reference model does NOT load here -- only same-group torch.optim.Adam state does."""
+    opt = Adam(reference_param_groups(rs, lr, color_grid_wd, material, emitter, pose_correction, pose_correction_wd), lr=lr,
+               betas=(0.9, 0.99), eps=1e-15, grad_scale=grad_scale)
     sched = None
     if warmup_steps:
         S = torch.optim.lr_scheduler

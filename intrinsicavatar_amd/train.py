@@ -293,10 +293,10 @@ def shade_front(rs, rays_o: Tensor, rays_d: Tensor, ray_indices: Tensor, t_start
     if pose:
         # pose_correction / SMPL parameters are being optimised (configs/config.yaml: pose_correction.enable_pose_correction):
         # the roots get their implicit-function derivative and the normal push-forward its blended-rotation derivative;
-        # the forward VALUES stay the ones the search kernels produced.
+        # the forward VALUES stay the ones the search kernels produced.  One node (deformer._PoseTerms): nothing is launched here,
+        # its backward is one fused kernel (SNARFDeformer.implicit_pose_terms is the same derivative as torch expressions)
         J_inv_win = d["J_inv"].reshape(-1, 3, 3)[win]
-        pts_cano, R = dfm.implicit_pose_terms(pts_cano, J_inv_win, valid)
-        c2w = c2w + (R - R.detach()) * valid[:, None, None].to(R.dtype)
+        pts_cano, c2w = dfm.pose_terms(pts_cano, c2w, J_inv_win, valid)
     geo_w = geo.effective_weights()
     out, grad_c = _SDFField.apply(pts_cano, geo.grid_params, *geo_w, geo.center, geo.scale, level_bits(), geo.inv_scale_host())
     # invalid points: sdf 1e5, feature 0, gradient [0,0,1] (snarf_deformer.py:192-231); valid ones: the normal push-forward with the

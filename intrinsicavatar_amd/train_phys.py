@@ -35,8 +35,27 @@ class _HashEncode(Function):
     def backward(ctx, g_enc):
         xp, table = ctx.saved_tensors
         g_table = L.zeros_like(table)
-        fields.hashgrid_backward(xp, g_enc.contiguous(), g_table)
-        return None, g_table
+        g_enc = g_enc.contiguous()
+        fields.hashgrid_backward(xp, g_enc, g_table)
+        g_xp = None
+        if ctx.needs_input_grad[0]:       # pose gradients: the hash Jacobian is recomputed here (not kept in forward), as train._Radiance does
+            _, jac = fields.hashgrid_forward(xp, table, with_jac=True)
+            g_xp = train._jac_contract_T(jac, g_enc)
+        return g_xp, g_table
+
+
+class _GridCoords(Function):
+    """fields.normalize_points with the derivative of its input: (x - center) / scale + 0.5 (pose gradients only)."""
+
+    @staticmethod
+    def forward(ctx, x, center, scale):
+        ctx.save_for_backward(scale)
+        return fields.normalize_points(x, center, scale)
+
+    @staticmethod
+    def backward(ctx, g):
+        (scale,) = ctx.saved_tensors
+        return g / scale, None, None
 
 
 class _MLP2(Function):
@@ -160,12 +179,16 @@ def shade_differentiable_phys(rs, material, emitter, rays_o: Tensor, rays_d: Ten
     geo, rad = rs.geometry, rs.radiance
     n_rays = packed_info.shape[0]
     dev = rays_o.device
-    # every hash level takes a gradient, no pose terms (train.shade_differentiable: the active levels, pose terms)
-    f = train.shade_front(rs, rays_o, rays_d, ray_indices, t_starts, t_ends, lambda: 0xFFFFFFFF, False)
+    # every hash level takes a gradient (train.shade_differentiable: the active levels); the pose terms as there, while tfs is optimised
+    f = train.shade_front(rs, rays_o, rays_d, ray_indices, t_starts, t_ends, lambda: 0xFFFFFFFF,
+                          rs.deformer.tfs.requires_grad and torch.is_grad_enabled())
     n_samples = t_starts.shape[0]
     # hash grid #2 once; radiance and material heads
-    with torch.no_grad():
-        xp2 = fields.normalize_points(f.d["pts_cano"], rad.center, rad.scale)
+    if f.pts_cano.requires_grad:          # pose terms attached: the primary samples' positions carry the gradient of the roots
+        xp2 = _GridCoords.apply(f.pts_cano, rad.center, rad.scale)
+    else:
+        with torch.no_grad():
+            xp2 = fields.normalize_points(f.d["pts_cano"], rad.center, rad.scale)
     enc2 = _HashEncode.apply(xp2, rad.grid_params)
     sh = _SH4.apply(f.refl01)
     rgbs = _MLP2.apply(1, 3, *rad.effective_weights(), enc2, xp2, f.feat, sh, f.normal_world)
